@@ -17,6 +17,11 @@ for the global loss / PSNR outside the timed region.
 Scaling modes: ``weak`` (default) = ``--blocks`` blocks PER GPU; ``strong`` = the blocks of ONE
 ``--image`` (padded to a multiple of the block) split over the ranks by ``dist.shard_range``.
 
+A plain run sets up, warms up, times exactly ``--steps`` steps once and prints the line.  ``--full`` adds what
+takes runs of its own: the repetition of a short timed region until MIN_TIMED_S, the single-image line, the CPU
+baseline and the GPU-vs-CPU parity legs.  ``--dump-outputs DIR`` writes the state the timed steps left behind
+(parameters, Adam slots, kernel lists, divergence flags of rank 0's blocks) as DIR/<name>.npy.
+
 Prints ONE JSON line on rank 0 (contract: see the task statement / DESIGN.md "Measurement").
 """
 import argparse
@@ -35,8 +40,10 @@ if ROOT not in sys.path:
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 SIMDS = 256 * 4                # MI355X: 256 CUs x 4 SIMD-32
 ENGINE_HZ = 2.4e9              # nominal engine clock; measured under this kernel: GRBM_GUI_ACTIVE / 8 / time = 2.41 GHz
-MIN_TIMED_S = 0.5              # the K timed steps are repeated from cloned start state until this much timed GPU work has been done
-                               # (median of the repetitions reported): a region an outside observer (gpu_busy sampling) can see
+MIN_TIMED_S = 0.5              # --full: the K timed steps are repeated from cloned start state until this much timed GPU work has been
+                               # done (median of the repetitions reported): a region an outside observer (gpu_busy sampling) can see
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: above this, the same seeded sample of blocks from every array
+DUMP_SAMPLE_SEED = 20260003
 
 
 def parse_args(argv=None):
@@ -57,11 +64,17 @@ def parse_args(argv=None):
     ap.add_argument("--loss-weights", action="store_true",
                     help="every block carries per-pixel loss weights (as the blocks of an image that is not a multiple of the block "
                          "do: the last eighth of every block gets weight 0); not the headline configuration")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: repetitions of a timed region shorter than 0.5 s, "
+                         "the single-image line, the CPU baseline and the GPU-vs-CPU parity legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the state they left (parameters, Adam slots, kernel lists, divergence "
+                         "flags; rank 0's blocks) as DIR/<name>.npy in float32 / float64, at most 64 MB in all")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and parity legs")
     ap.add_argument("--no-quantize-pis", action="store_true",
                     help="diagnostic: run the constructor default (pis not fake-quantised) instead of the CLI default")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary single-image measurement")
-    ap.add_argument("--no-reps", action="store_true", help="time the K steps once even when they take < 0.5 s")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary single-image measurement")
+    ap.add_argument("--no-reps", action="store_true", help="with --full: time the K steps once even when they take < 0.5 s")
     ap.add_argument("--max-reps", type=int, default=2000)
     ap.add_argument("--tiling-scope", choices=("global", "local"), default="global",
                     help="strong scaling: choose the kernel tiling (= the summation order inside a block) from the block "
@@ -202,6 +215,25 @@ def load_profile_json(name):
         except Exception:
             return {}
     return {}
+
+
+def dump_outputs(dirname, arrays):
+    """Writes ``arrays`` (name -> numpy array, blocks on axis 0) as DIR/<name>.npy: float32 stays float32, everything else
+    becomes float64 (exact for the int32 kernel lists).  Above DUMP_LIMIT_BYTES in all, every array keeps the same
+    seeded sample of blocks, whose indices go to DIR/sample_block_index.npy."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64) for k, a in arrays.items()}
+    B = min(len(a) for a in arrays.values())
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES and B > 0:
+        per_block = total / B + 8                                      # + the float64 index of the block
+        n = max(1, min(B, int(DUMP_LIMIT_BYTES // per_block)))
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(B, n, replace=False))
+        arrays = {k: np.ascontiguousarray(a[idx]) for k, a in arrays.items()}
+        arrays["sample_block_index"] = idx.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
 
 
 def worker(args):
@@ -364,8 +396,8 @@ def worker(args):
         del p2, st2, a2, d2
     run_steps(args.warmup)
 
-    # ---- the timed region: EXACTLY K steps between barrier + synchronize, MAX over ranks.  When that is shorter than
-    # MIN_TIMED_S it is repeated from the cloned start state (same K steps, same trajectory) and the median is reported.
+    # ---- the timed region: EXACTLY K steps between barrier + synchronize, MAX over ranks.  With --full, when that is shorter
+    # than MIN_TIMED_S it is repeated from the cloned start state (same K steps, same trajectory) and the median is reported.
     def snapshot():
         return ({k: v.clone() for k, v in params.items()}, {k: v.clone() for k, v in state.m.items()},
                 {k: v.clone() for k, v in state.v.items()},
@@ -391,12 +423,13 @@ def worker(args):
             return float(tt.item()), t_local
         return t_local, t_local
 
-    start = snapshot()
+    repeat = args.full and not args.no_reps
+    start = snapshot() if repeat else None
     events = []
     times, locals_ = [], []
     t, tl = timed_once(events)
     times.append(t); locals_.append(tl)
-    if t < MIN_TIMED_S and not args.no_reps:
+    if t < MIN_TIMED_S and repeat:
         # repeated until MIN_TIMED_S of timed work has been done (at least three times): every rank sees the same all-reduced
         # times, so every rank takes the same decision
         while (len(times) < 3 or sum(times) < MIN_TIMED_S) and len(times) < args.max_reps:
@@ -406,6 +439,16 @@ def worker(args):
     reps = len(times)
     t_wall = float(np.median(times))
     del start
+
+    # ---- what the last timed step left for a caller of the fit: before the evaluation pass below, which may prune the lists
+    if args.dump_outputs and rank == 0:
+        host = lambda t: t.detach().cpu().numpy()
+        arrays = {k: host(v) for k, v in params.items()}
+        arrays.update({"adam_m_" + k: host(v) for k, v in state.m.items()})
+        arrays.update({"adam_v_" + k: host(v) for k, v in state.v.items()})
+        arrays["active"] = host(active)
+        arrays["diverged"] = host(diverged)
+        dump_outputs(args.dump_outputs, arrays)
 
     # per-launch device time from HIP events on the launch stream (full-size launches only)
     full = [e0.elapsed_time(e1) for (e0, e1, n) in events if n == ipl] if on_gpu else []
@@ -445,7 +488,7 @@ def worker(args):
 
     # ---- secondary: BASELINE configs[1] literally (ONE 512x512 image = 1024 blocks), rank 0 only ----
     single = None
-    if rank == 0 and on_gpu and not args.no_extras and shape == (16, 16) and C == 1 and B >= 1024:
+    if rank == 0 and on_gpu and args.full and not args.no_extras and shape == (16, 16) and C == 1 and B >= 1024:
         Bs = 1024
         eng1 = BlockEngine(EngineConfig(block_shape=shape, channels=C, kernels=K, use_yuv=use_yuv, quantize_pis=True))
         t1 = target[:Bs].contiguous()
@@ -560,7 +603,7 @@ def worker(args):
             out["valu"] = {"bound": "fp32 VALU issue (2 cycles per wave64 instruction per SIMD-32)",
                            "valu_insts_per_wave_px_iter": ipp, "issue_util": round(rate / peak, 4),
                            "issue_util_profiled": pm.get("issue_util"), "source": pm.get("source")}
-        if n_gpus == 1 and not args.no_cpu_baseline and args.scaling == "weak":
+        if n_gpus == 1 and args.full and not args.no_cpu_baseline and args.scaling == "weak":
             # ---- CPU baseline on a bounded sample + the parity criterion at this step count.  "port" = the plain-C
             # restatement of the reference's TF graph (oracle/smoe_oracle.c); the reference itself cannot run: TensorFlow 1.x
             # is not in this image and nothing can be installed.

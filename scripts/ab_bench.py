@@ -30,7 +30,7 @@ def main():
     res = {l: [] for l in libs}
     for r in range(rounds):
         for l in libs:
-            out = subprocess.run([sys.executable, "-c", CHILD, ROOT, os.path.abspath(l)] + bargs + ["--no-cpu-baseline", "--no-extras"],
+            out = subprocess.run([sys.executable, "-c", CHILD, ROOT, os.path.abspath(l)] + bargs + ["--full", "--no-cpu-baseline", "--no-extras"],
                                  stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
             line = [x for x in out.stdout.splitlines() if x.startswith("{")]
             if not line:

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Team tiling (csrc/smoe_team.hip.h) against the regular kernels over the batch sizes below ~16 000 blocks.
 # usage: scripts/bench_team.sh  (prints one line per run; profiles/r03/bench_team.txt)
-run() { timeout -k 10 200 python bench.py --no-cpu-baseline --no-extras --steps 100 --warmup 10 "$@" 2>/dev/null | python -c "
+run() { timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-extras --steps 100 --warmup 10 "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']
 print('%-22s B=%-6d %-26s %10.1f Mpx-it/s  frac %.3f  ms/launch %.3f  psnr %.2f->%.2f (median %.2f)' % ('x'.join(map(str,d['config']['block_shape']))+' C%d K%d'%(d['config']['channels'],d['config']['kernels']), d['config']['blocks_per_gpu'], d['config']['kernel_variant'], d['value'], r['frac'], r['kernel_ms_per_launch'], d['initial_psnr_db'], d['final_psnr_db'], d['final_median_block_psnr_db']))"; }

@@ -6,8 +6,8 @@ ROOT="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 cd "$ROOT" || exit 1
 mkdir -p "$OUT"
 export PYTHONPATH="$ROOT"
-timeout -k 10 400 python bench.py > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err" || echo "bench default rc=$?"
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 > "$OUT/bench_n1_steps20.json" 2> "$OUT/bench_n1_steps20.err" || echo "bench steps20 rc=$?"
+timeout -k 10 400 python bench.py --full > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err" || echo "bench default rc=$?"
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > "$OUT/bench_n1_steps20.json" 2> "$OUT/bench_n1_steps20.err" || echo "bench steps20 rc=$?"
 bash scripts/prof_bench.sh "$OUT" --steps 20 --warmup 5 > "$OUT/prof_bench.log" 2>&1
 mv "$OUT/bench_under_rocprof.json" "$OUT/bench_n1_under_rocprof.json" 2>/dev/null
 rm -rf "$OUT/trace"

@@ -60,12 +60,55 @@ def test_four_ranks_one_of_them_without_blocks():
 
 
 def test_short_timed_region_is_repeated_from_cloned_state():
-    d = _run(["--gpus", "1", "--blocks", "4"])
+    d = _run(["--gpus", "1", "--blocks", "4", "--full"])
     assert d["config"]["reps"] >= 3 and len(d["config"]["timed_s_each_rep"]) == min(12, d["config"]["reps"])
     assert d["config"]["timed_region_s_total"] >= 0.45 or d["config"]["reps"] == 2000       # an externally visible timed region
-    once = _run(["--gpus", "1", "--blocks", "4", "--no-reps"])
+    once = _run(["--gpus", "1", "--blocks", "4", "--full", "--no-reps"])
     assert once["config"]["reps"] == 1
     assert abs(once["final_psnr_db"] - d["final_psnr_db"]) < 1e-9      # every repetition replays the same K steps
+
+
+def test_plain_run_times_the_requested_steps_once():
+    """Without --full the K steps are timed once, however short, and the line carries nothing of the --full legs."""
+    d = _run(["--gpus", "1", "--blocks", "4"])
+    assert d["steps"] == 3 and d["config"]["reps"] == 1 and len(d["config"]["timed_s_each_rep"]) == 1
+    assert abs(d["ms_per_step"] * 3 / 1e3 - d["config"]["timed_region_s_total"]) <= 6e-5   # the total is rounded to 0.1 ms
+    for key in ("cpu_baseline", "parity", "single_image"):
+        assert key not in d
+    full = _run(["--gpus", "1", "--blocks", "4", "--full"])
+    assert full["state_digest"] == d["state_digest"]                  # the same K steps from the same start
+
+
+def test_dump_outputs_writes_the_fitted_state(tmp_path):
+    """--dump-outputs DIR: one .npy per array of the fitted state, float32 / float64, the same from run to run."""
+    import numpy as np
+    a, b = tmp_path / "a", tmp_path / "b"
+    _run(["--gpus", "1", "--blocks", "6", "--dump-outputs", str(a)])
+    _run(["--gpus", "1", "--blocks", "6", "--dump-outputs", str(b)])
+    names = sorted(os.listdir(a))
+    assert names == sorted(os.listdir(b))
+    for n in ("pis.npy", "musX.npy", "A_diagonal.npy", "nu_e.npy", "adam_m_musX.npy", "adam_v_pis.npy", "active.npy",
+              "diverged.npy"):
+        assert n in names, n
+    for n in names:
+        x, y = np.load(a / n), np.load(b / n)
+        assert x.dtype in (np.float32, np.float64) and len(x) == 6, n
+        assert np.array_equal(x, y), n
+    assert np.all(np.load(a / "active.npy") > 0)                      # kernel-list bit masks, exact in float64
+
+
+def test_dump_outputs_samples_the_same_blocks_above_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 2000)
+    x = np.arange(100 * 6, dtype=np.float32).reshape(100, 6)
+    k = np.arange(100, dtype=np.int32) * 3
+    bench.dump_outputs(str(tmp_path), {"x": x, "k": k})
+    idx = np.load(tmp_path / "sample_block_index.npy")
+    xs, ks = np.load(tmp_path / "x.npy"), np.load(tmp_path / "k.npy")
+    assert 0 < len(idx) < 100 and np.all(np.diff(idx) > 0) and xs.dtype == np.float32 and ks.dtype == np.float64
+    assert xs.nbytes + ks.nbytes + idx.nbytes <= 2000
+    assert np.array_equal(xs, x[idx.astype(int)]) and np.array_equal(ks, k[idx.astype(int)])
 
 
 def test_torchrun_environment_is_used_as_is(tmp_path):

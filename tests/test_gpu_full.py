@@ -348,7 +348,7 @@ def test_bench_line_keeps_the_driver_contract():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "10",
-                          "--blocks", "4096", "--cpu-budget-s", "1.5", "--clock-warm-iters", "100"],
+                          "--blocks", "4096", "--cpu-budget-s", "1.5", "--clock-warm-iters", "100", "--full"],
                          capture_output=True, text=True, timeout=300, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -366,6 +366,32 @@ def test_bench_line_keeps_the_driver_contract():
     c = d["cpu_baseline"]
     assert c["kind"] in ("port", "reference") and c["cores"] >= 1 and c["value"] > 0 and c["sample"]
     assert abs(d["value"] - 4096 * 256 * 30 / (d["ms_per_step"] * 30 / 1e3) / 1e6) / d["value"] < 0.02
+
+
+def test_bench_plain_run_dumps_the_same_fitted_state_every_time(tmp_path):
+    """A plain bench run (no --full) times the requested steps once, carries none of the --full legs, and its
+    --dump-outputs files are equal from run to run."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines = []
+    for name in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+                              "--blocks", "4096", "--dump-outputs", str(tmp_path / name)],
+                             capture_output=True, text=True, timeout=300, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines += [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 2
+    for d in lines:
+        assert d["steps"] == 20 and d["config"]["reps"] == 1 and d["ms_per_step"] > 0
+        assert "cpu_baseline" not in d and "single_image" not in d and "parity" not in d
+    assert lines[0]["state_digest"] == lines[1]["state_digest"]
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert "musX.npy" in names and "active.npy" in names and names == sorted(os.listdir(tmp_path / "b"))
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype in (np.float32, np.float64) and len(x) == 4096 and np.array_equal(x, y), n
 
 
 def test_facade_pads_kernel_counts_without_their_own_kernel():
