@@ -182,6 +182,38 @@ int smoe_checkpoint_best(smoe_handle h, int32_t num_blocks, const float* loss, f
 int smoe_reduce_scalars(smoe_handle h, int32_t num_blocks, const float* loss, const float* sse,
                         const uint32_t* active, double* out_dev, void* stream);
 
+/* Decoder: evaluate fitted block models on a separable sampling grid and store the samples at their place in the
+ * stitched image.  Unlike smoe_forward it needs no target and computes no loss; the sample grid is free (zoom, a finer
+ * pitch, frames between the fitted ones), and the output is the interleaved row-major image [E_0, E_1(, E_2), C] that
+ * get_reconstruction() returns, not block planes.
+ *   first_block, num_blocks  the blocks [first_block, first_block + num_blocks) of the image-wide block grid, row-major
+ *                            over grid[] with the last axis innermost (sliding_window order); a rank that holds these
+ *                            blocks renders its share into a full-size buffer
+ *   p, active                leading axis = num_blocks (the shard), as in smoe_forward; active [num_blocks] is only read,
+ *                            NULL = every kernel on the list.  Kernels count when listed and pis > 0; the parameters go
+ *                            through the handle's fake quantisation (quantize_pis, quantization_mode 2 / 3 with the
+ *                            centre grid of smoe_set_center_grid, indexed like p) exactly as in smoe_forward
+ *   axis_coords[l], samples[l]  per axis a DEVICE table of samples[l] fp32 coordinates in block units (the unit in which
+ *                            the training lattice is linspace(0, 1, block_shape[l])), the same for all blocks; sample
+ *                            (j_0, j_1[, j_2]) of a block is evaluated at (axis_coords[0][j_0], axis_coords[1][j_1], ...).
+ *                            Values outside [0, 1] are legal
+ *   grid[l], extent[l]       blocks per axis and extent E_l in samples of the WHOLE image, 1 <= E_l <= grid[l]*samples[l];
+ *                            block (g_0, g_1[, g_2]) owns positions g_l*samples[l] + j_l, positions >= E_l are not written
+ *                            (the crop of a ragged image).  Offsets into the image are 64-bit
+ *   image, image_format      SMOE_IMAGE_F32: the lattice values smoe_forward writes into recon (bit-identical on the
+ *                            training lattice for the same handle state and num_blocks / smoe_set_total_blocks);
+ *                            SMOE_IMAGE_U8: the lattice indices k of k / (2^precision - 1) (precision <= 8)
+ *   argmax                   [E_0, E_1(, E_2)] uint8 or NULL: first maximum among the kernels with influence on the
+ *                            sample; 255 where no kernel has influence (smoe_forward replaces such pixels by a block-wide
+ *                            choice made on the training lattice; a render grid has none, so the 255 stays)
+ * Entries [dim .. 2] of the arrays are ignored.  Only positions owned by the rendered blocks are written.  Stores are
+ * 16-byte wide when image / argmax are 16-byte aligned. */
+#define SMOE_IMAGE_F32 0
+#define SMOE_IMAGE_U8 1
+int smoe_render(smoe_handle h, int32_t first_block, int32_t num_blocks, const smoe_params* p, const uint32_t* active,
+                const float* const axis_coords[3], const int32_t samples[3], const int32_t grid[3],
+                const int64_t extent[3], void* image, int32_t image_format, uint8_t* argmax, void* stream);
+
 /* Name of the kernel variant smoe_fit would launch for num_blocks (diagnostics / profiles). */
 const char* smoe_fit_variant(smoe_handle h, int32_t num_blocks);
 

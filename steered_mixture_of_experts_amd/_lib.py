@@ -19,6 +19,8 @@ SMOE_ERR_INVALID = -1
 SMOE_ERR_UNSUPPORTED = -2
 SMOE_ERR_HIP = -3
 SMOE_ERR_NO_DEVICE = -4
+SMOE_IMAGE_F32 = 0
+SMOE_IMAGE_U8 = 1
 
 EXPORTS = (
     "smoe_create", "smoe_destroy", "smoe_is_supported", "smoe_padded_kernels", "smoe_get_coords", "smoe_forward",
@@ -28,6 +30,7 @@ EXPORTS = (
     "smoe_shared_forward", "smoe_shared_accumulate", "smoe_shared_apply", "smoe_shared_grad_buffer",
     "smoe_shared_fit", "smoe_shared_update_kernel_list", "smoe_shared_set_loss_weights",
     "smoe_set_center_grid", "smoe_shared_set_center_grid", "smoe_set_total_blocks", "smoe_padded_kernels_full", "smoe_shared_discard", "smoe_set_sampling",
+    "smoe_render",
 )
 
 
@@ -104,6 +107,8 @@ def load() -> C.CDLL:
     lib.smoe_update_kernel_list.argtypes = [vp, i32, C.POINTER(SmoeParams), fp, vp]
     lib.smoe_checkpoint_best.argtypes = [vp, i32, fp, fp, C.POINTER(SmoeParams), C.POINTER(SmoeParams), vp]
     lib.smoe_reduce_scalars.argtypes = [vp, i32, fp, fp, fp, fp, vp]
+    lib.smoe_render.argtypes = [vp, i32, i32, C.POINTER(SmoeParams), fp, C.POINTER(C.c_void_p), C.POINTER(C.c_int32),
+                                C.POINTER(C.c_int32), C.POINTER(C.c_int64), fp, i32, fp, vp]
     lib.smoe_fit_variant.argtypes = [vp, i32]
     lib.smoe_fit_variant.restype = C.c_char_p
     lib.smoe_fit_occupancy.argtypes = [vp, i32]

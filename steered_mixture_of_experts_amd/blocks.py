@@ -69,6 +69,23 @@ def blocks_to_image(blocks: np.ndarray, domain_shape: Sequence[int], block_shape
     return arr[sl]
 
 
+def render_axis(n: int, m: int) -> np.ndarray:
+    """Coordinates (block units, float32) of ``m`` render samples along a block axis fitted on ``n`` pixels -- the one
+    definition of the mapping behind ``Smoe.render``.  ``m == n``: the training lattice ``linspace(0, 1, n)`` itself;
+    otherwise the centres of ``m`` equal cells over the block's pixel footprint, ``((j + 0.5) n / m - 0.5) / (n - 1)``:
+    an output pixel of a 2x image sits where a 2x finer sensor would have it, and the first / last samples overhang the
+    lattice by less than half a source pixel.  Computed in float64, rounded once."""
+    n, m = int(n), int(m)
+    if n < 1 or m < 1:
+        raise ValueError("render_axis: n and m must be >= 1")
+    if n == 1:
+        return np.zeros((m,), dtype=np.float32)
+    if m == n:
+        return np.linspace(0, 1, n).astype(np.float32)
+    j = np.arange(m, dtype=np.float64)
+    return (((j + 0.5) * n / m - 0.5) / (n - 1)).astype(np.float32)
+
+
 def to_planar(blocks: np.ndarray) -> np.ndarray:
     """(B, *block_shape, C) -> (B, C, N): the C-ABI target layout (include/smoe_hip.h)."""
     B, C = blocks.shape[0], blocks.shape[-1]

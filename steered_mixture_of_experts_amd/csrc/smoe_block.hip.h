@@ -445,6 +445,7 @@ template <int D, int C, int K>
 struct PixelOut {
     float wt[K];    // masked gate
     float q[C];     // quantised reconstruction
+    float kq[C];    // its lattice index (q = kq * scale), for the uint8 store of the render kernel
 };
 
 // One pixel.  TRAIN: accumulate raw gradient sums into acc[] (layout = packed params,
@@ -538,7 +539,8 @@ __device__ __forceinline__ void pixel(const BlockRegs<D, C, K>& R, const KernelC
     for (int c = 0; c < C; ++c) {
         // clip_by_value(0,1) then the fake-quant clamp to its nudged range: kc.nudged_max = min(1, nudged max)
         const float yc = __builtin_amdgcn_fmed3f(y[c], 0.0f, kc.nudged_max);
-        o.q[c] = floorf(fmaf(yc, kc.inv_scale, 0.5f)) * kc.scale;
+        o.kq[c] = floorf(fmaf(yc, kc.inv_scale, 0.5f));
+        o.q[c] = o.kq[c] * kc.scale;
         const float diff = o.q[c] - t[c];
         const float ad = fabsf(diff) - kc.epsm;
         acc[Lt::S_SSE] = fmaf(diff, diff, acc[Lt::S_SSE]);
@@ -2683,7 +2685,8 @@ int fit_occupancy(int N, bool has_lw, int hoist, bool pair) {
       &launch_readmit_quant<D, C, K, G, W>, &launch_fit_quant<D, C, K, G, W>, &launch_fwd_quant<D, C, K, G, W>, \
       &launch_fit_ic<D, C, K, G, W>, &launch_fwd_ic<D, C, K, G, W>, \
       team_fit_ptr<D, C, K, G, W>(), team_lds_ptr<D, C, K, G, W>(), team_occ_ptr<D, C, K, G, W>(), \
-      duo_fit_ptr<D, C, K, G>(), duo_lds_ptr<D, C, K, G>(), duo_occ_ptr<D, C, K, G>() }
+      duo_fit_ptr<D, C, K, G>(), duo_lds_ptr<D, C, K, G>(), duo_occ_ptr<D, C, K, G>(), \
+      &launch_render<D, C, K, (SMOE_FULL != 0)> }
 
 // Reduced instantiation for the (dim, channels, kernels) triples outside the BASELINE shapes: the margin loss with and
 // without train_inverse_cov (quantize_pis included: it lives in the default kernels); ssim_opt and quantization_mode
@@ -2693,7 +2696,8 @@ int fit_occupancy(int N, bool has_lw, int hoist, bool pair) {
       nullptr, nullptr, nullptr, &launch_readmit_quant<D, C, K, G, W>, nullptr, nullptr, \
       &launch_fit_ic<D, C, K, G, W>, &launch_fwd_ic<D, C, K, G, W>, \
       team_fit_ptr<D, C, K, G, W>(), team_lds_ptr<D, C, K, G, W>(), team_occ_ptr<D, C, K, G, W>(), \
-      duo_fit_ptr<D, C, K, G>(), duo_lds_ptr<D, C, K, G>(), duo_occ_ptr<D, C, K, G>() }
+      duo_fit_ptr<D, C, K, G>(), duo_lds_ptr<D, C, K, G>(), duo_occ_ptr<D, C, K, G>(), \
+      &launch_render<D, C, K, (SMOE_FULL != 0)> }
 
 }  // namespace smoe
 #endif

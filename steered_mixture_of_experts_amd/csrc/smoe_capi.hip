@@ -754,6 +754,64 @@ int smoe_fit(smoe_handle h, int32_t num_blocks, const float* target, const float
     return check_debug_word(h, (hipStream_t)stream, "smoe_fit");
 }
 
+int smoe_render(smoe_handle h, int32_t first_block, int32_t num_blocks, const smoe_params* p, const uint32_t* active,
+                const float* const axis_coords[3], const int32_t samples[3], const int32_t grid[3],
+                const int64_t extent[3], void* image, int32_t image_format, uint8_t* argmax, void* stream) {
+    if (!h) return fail(SMOE_ERR_INVALID, "smoe_render: null handle");
+    if (first_block < 0 || num_blocks < 0) return fail(SMOE_ERR_INVALID, "smoe_render: negative first_block / num_blocks");
+    if (!params_ok(p)) return fail(SMOE_ERR_INVALID, "smoe_render: p (all six parameter tensors) is required");
+    if (!image) return fail(SMOE_ERR_INVALID, "smoe_render: image is required");
+    if (!axis_coords || !samples || !grid || !extent)
+        return fail(SMOE_ERR_INVALID, "smoe_render: axis_coords, samples, grid and extent are required");
+    if (image_format != SMOE_IMAGE_F32 && image_format != SMOE_IMAGE_U8)
+        return fail(SMOE_ERR_INVALID, "smoe_render: image_format must be SMOE_IMAGE_F32 or SMOE_IMAGE_U8");
+    const int D = h->cfg.dim;
+    long long total = 1;
+    for (int l = 0; l < D; ++l) {
+        const std::string ax = "[" + std::to_string(l) + "]";
+        if (!axis_coords[l]) return fail(SMOE_ERR_INVALID, "smoe_render: axis_coords" + ax + " is null");
+        if (samples[l] < 1) return fail(SMOE_ERR_INVALID, "smoe_render: samples" + ax + " must be >= 1");
+        if (grid[l] < 1) return fail(SMOE_ERR_INVALID, "smoe_render: grid" + ax + " must be >= 1");
+        if (extent[l] < 1 || extent[l] > (long long)grid[l] * samples[l])
+            return fail(SMOE_ERR_INVALID, "smoe_render: extent" + ax + " must be 1 .. grid * samples");
+        total *= grid[l];
+        if (total > 0x7fffffffLL) return fail(SMOE_ERR_INVALID, "smoe_render: grid has more than 2^31 blocks");
+    }
+    if ((long long)first_block + num_blocks > total)
+        return fail(SMOE_ERR_INVALID, "smoe_render: first_block + num_blocks exceeds prod(grid)");
+    if (image_format == SMOE_IMAGE_U8 && h->cfg.precision > 8)
+        return fail(SMOE_ERR_UNSUPPORTED, "smoe_render: SMOE_IMAGE_U8 needs precision <= 8");
+    if (num_blocks == 0) return SMOE_OK;
+    // the tiling -- and with it the hoisting level, i.e. the order of a sample's fused multiply-adds -- smoe_forward takes
+    // for this handle and this many blocks
+    const smoe::Variant* v = find_variant(h, num_blocks, false);
+    if (!v || !v->render) return fail(SMOE_ERR_UNSUPPORTED, "smoe_render: no kernel variant for this handle");
+    const int hl = h->cfg.ssim_opt ? 0 : hoist_level(h, v);
+    HIP_TRY(hipSetDevice(h->cfg.device), "hipSetDevice");
+    smoe::RenderArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.p = *p; a.active = active;
+    for (int l = 0; l < D; ++l) { a.ax[l] = axis_coords[l]; a.m[l] = samples[l]; a.grid[l] = grid[l]; a.ext[l] = extent[l]; }
+    for (int l = D; l < SMOE_MAX_DIM; ++l) { a.m[l] = 1; a.grid[l] = 1; a.ext[l] = 1; }
+    a.first = first_block; a.nb = num_blocks;
+    a.image = image; a.fmt = image_format; a.argmax = argmax;
+    a.mus_grid = h->mus_grid;
+    a.vec_img = ((uintptr_t)image % 16 == 0) ? 1 : 0;
+    a.vec_arg = ((uintptr_t)argmax % 16 == 0) ? 1 : 0;
+    a.kc = h->kc;
+#if !SMOE_HOST_TEST
+    {
+        const hipError_t e = v->render(a, hl, v->G, (hipStream_t)stream);
+        if (e == hipErrorNotSupported)
+            return fail(SMOE_ERR_UNSUPPORTED, "smoe_render: this sample grid does not fit the kernel's LDS (or the graph variant is not built for the triple)");
+        if (e != hipSuccess) return fail_hip(e, "smoe_render launch");
+    }
+#else
+    (void)hl;
+#endif
+    return SMOE_OK;
+}
+
 int smoe_update_kernel_list(smoe_handle h, int32_t num_blocks, const smoe_params* p,
                             uint32_t* active, void* stream) {
     if (!h) return fail(SMOE_ERR_INVALID, "smoe_update_kernel_list: null handle");

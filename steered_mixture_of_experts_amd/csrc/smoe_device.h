@@ -114,6 +114,27 @@ struct ReduceArgs {
     int B, N;
 };
 
+// smoe_render (smoe_render.hip.h): evaluate the blocks [first, first + nb) of an image-wide block grid on a separable sample
+// grid and store the samples into the stitched image.  The launcher fills the geometry fields.
+struct RenderArgs {
+    smoe_params p;            // leading axis = nb (the shard)
+    const uint32_t* active;   // [nb] or null = every kernel listed
+    const float* ax[SMOE_MAX_DIM];   // per-axis sample coordinates in block units
+    int m[SMOE_MAX_DIM];      // samples per block and axis
+    int grid[SMOE_MAX_DIM];   // blocks per axis of the whole image
+    long long ext[SMOE_MAX_DIM];     // extent of the whole image in samples
+    int first, nb;
+    void* image;              // [E_0, E_1(, E_2), C] float32 or uint8
+    int fmt;                  // SMOE_IMAGE_F32 / SMOE_IMAGE_U8
+    uint8_t* argmax;          // [E_0, E_1(, E_2)] or null
+    const float* mus_grid;    // as in FitArgs, indexed like p
+    int vec_img, vec_arg;     // the plane's base is 16-byte aligned: vector stores
+    int NB, CL, RP;           // blocks per workgroup, innermost samples per block and pass, outer sample tuples per step
+    int chunks, line0;        // workgroups per grid line, first grid line of the launch
+    int off_par, off_stage;   // float offsets of the block images / the staging buffers in the dynamic LDS
+    KernelConsts kc;
+};
+
 struct Variant {
     int D, C, K, G, W;
     const char* name;
@@ -137,6 +158,8 @@ struct Variant {
     hipError_t (*fit_duo)(const FitArgs&, int hoist_level, hipStream_t);
     size_t (*duo_lds_bytes)(int N, bool has_lw, int hoist_level);      // (size_t)-1: the triple has too many slots
     int (*duo_waves_per_cu)(int N, bool has_lw, int hoist_level);
+    // decoder (smoe_render.hip.h; the same entry on every tiling of a triple): hl = hoisting level, lanes = the tiling's G
+    hipError_t (*render)(const RenderArgs&, int hl, int lanes, hipStream_t);
 };
 
 // ---- shared-kernel image mode (smoe_shared.hip) ----------------------------------------------

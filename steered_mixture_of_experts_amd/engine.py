@@ -223,6 +223,50 @@ class BlockEngine:
                                          int(update_active), self._stream()))
         return out
 
+    def render(self, params, active, axes, grid, extent, first_block=0, out=None, dtype=torch.float32,
+               want_argmax=False):
+        """Decode: evaluate the blocks ``[first_block, first_block + B)`` of an image-wide block ``grid`` on the separable
+        sample grid ``axes`` (one float32 device table per axis, block units) into the stitched image
+        ``[*extent, C]`` (include/smoe_hip.h: smoe_render).  ``active`` [B] int32 or None (every kernel listed).  ``out``: a
+        full-size image to render into (only the positions of the rendered blocks are written); otherwise a new one,
+        zero-filled where this call renders only a part.  Returns the image, with ``want_argmax`` also the uint8 kernel
+        map ``[*extent]`` (255: no kernel has influence; 255 as well where no block was rendered)."""
+        d, Cc = self.cfg.dim, self.cfg.channels
+        B = int(params["pis"].shape[0])
+        self._check_params(params, B)
+        if dtype not in (torch.float32, torch.uint8):
+            raise ValueError("render: dtype must be torch.float32 or torch.uint8")
+        if len(axes) != d or len(grid) != d or len(extent) != d:
+            raise ValueError(f"render: axes, grid and extent need {d} entries")
+        for t in axes:
+            if t.dim() != 1 or t.numel() < 1 or t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"render: every axis table must be a contiguous 1-d float32 tensor on {self.device}")
+        grid = [int(g) for g in grid]
+        extent = [int(e) for e in extent]
+        total = 1
+        for g in grid:
+            total *= g
+        if active is not None and (tuple(active.shape) != (B,) or active.dtype != torch.int32 or active.device != self.device):
+            raise ValueError(f"render: active must be int32 [{B}] on {self.device}")
+        shape = tuple(extent) + (Cc,)
+        if out is None:
+            out = (torch.empty if (first_block == 0 and B == total) else torch.zeros)(shape, dtype=dtype, device=self.device)
+        elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"render: out must be a contiguous {dtype} tensor {shape} on {self.device}")
+        am = None
+        if want_argmax:
+            am = torch.full(tuple(extent), 255, dtype=torch.uint8, device=self.device)
+        if B > 0:
+            cp = self._cparams(params)
+            tabs = (C.c_void_p * 3)(*([t.data_ptr() for t in axes] + [None] * (3 - d)))
+            m3 = (C.c_int32 * 3)(*([int(t.numel()) for t in axes] + [1] * (3 - d)))
+            g3 = (C.c_int32 * 3)(*(grid + [1] * (3 - d)))
+            e3 = (C.c_int64 * 3)(*(extent + [1] * (3 - d)))
+            fmt = _lib.SMOE_IMAGE_U8 if dtype == torch.uint8 else _lib.SMOE_IMAGE_F32
+            _lib.check(self.lib.smoe_render(self._h, int(first_block), B, C.byref(cp), _ptr(active), tabs, m3, g3, e3,
+                                            _ptr(out), fmt, _ptr(am), self._stream()))
+        return (out, am) if want_argmax else out
+
     def fit(self, target, params, state: AdamState, active, n_iters: int, loss_w=None, diverged=None,
             loss0=None, loss_out=None, sse_out=None, loss_w_is_sample=False):
         """loss_w_is_sample: ``loss_w`` is a pixel sub-sample (N / n for the drawn pixels, 0 otherwise; smoe.py:1664-1667):

@@ -463,6 +463,10 @@ class Smoe:
                     diverged=self._diverged, loss0=self._loss0, loss_out=loss, sse_out=sse,
                     **({} if sub_w is None else {"loss_w_is_sample": True}))
         else:
+            if update_reconstruction:
+                # the pass evaluates with the kernel lists it starts from and prunes them afterwards: render() of the
+                # same state evaluates with these
+                self._recon_active = self._active.clone()
             out = eng.forward(self._target, self._params, self._active, loss_w=self._loss_w,
                               want_recon=update_reconstruction, want_argmax=update_reconstruction,
                               want_gate=update_reconstruction)
@@ -625,6 +629,86 @@ class Smoe:
         if not self.qvalid:
             self.run_batched(train=False, update_reconstruction=True, with_quantized_params=True)
         return self.qreconstruction_image
+
+    def render(self, scale=None, samples_per_block=None, dtype=np.float32, quantized=False, want_argmax=False,
+               to_host=True):
+        """Decode the fitted blocks on another sampling grid, on the device (the engine's ``render``): every block is a
+        continuous function of the coordinate, so zooming, a finer pitch or frames between the fitted ones are "evaluate
+        the same model somewhere else" -- no pixel is interpolated.
+        ``scale``: a number or one per axis, ``m_l = round(scale_l * n_l)`` samples per block (at least 1);
+        ``samples_per_block``: the ``m_l`` themselves (a number or one per axis); neither: the training lattice.
+        Sample positions: ``blocks.render_axis``.  Output extent ``E_l = image.shape[l] * m_l // n_l`` (the padding of a
+        ragged image is cropped), layout ``[*E, C]`` as ``get_reconstruction()``; ``dtype`` float32 (lattice values) or
+        uint8 (lattice indices).  ``quantized``: render ``rparams`` (what ``get_qreconstruction`` evaluates).
+        ``want_argmax``: also the map of global kernel ids ``[*E]`` (int64, block offset added as in
+        ``get_weight_matrix_argmax``; -1 where no kernel has influence on the sample).  ``to_host=False`` returns device
+        tensors.  Several ranks: every rank renders its blocks and the images are summed; the result is the same on
+        every rank and for every number of ranks."""
+        d, n = self.dim_domain, self.batch_size_valued
+        if scale is not None and samples_per_block is not None:
+            raise ValueError("render: give scale or samples_per_block, not both")
+        if samples_per_block is not None:
+            spb = list(np.atleast_1d(samples_per_block))
+            spb = spb * d if len(spb) == 1 else spb
+            if len(spb) != d:
+                raise ValueError(f"render: samples_per_block needs one value or {d}")
+            m = [int(v) for v in spb]
+        else:
+            sc = list(np.atleast_1d(1 if scale is None else scale))
+            sc = sc * d if len(sc) == 1 else sc
+            if len(sc) != d:
+                raise ValueError(f"render: scale needs one value or {d}")
+            m = [max(1, int(round(float(v) * nl))) for v, nl in zip(sc, n)]
+        if min(m) < 1:
+            raise ValueError("render: at least one sample per block and axis")
+        extent = [max(1, int(self.image.shape[l]) * m[l] // n[l]) for l in range(d)]
+        npdt = np.dtype(dtype)
+        if npdt not in (np.dtype(np.float32), np.dtype(np.uint8)):
+            raise ValueError("render: dtype must be float32 or uint8")
+        tdt = torch.uint8 if npdt == np.dtype(np.uint8) else torch.float32
+        eng = self._engine
+        if not hasattr(eng, "render"):
+            raise NotImplementedError("this engine has no render()")
+        dev = eng.device
+        if quantized:
+            assert self.rparams is not None, "quantize_params + rescaler first (smoe.py:1499-1501)"
+            rp = {k: np.ascontiguousarray(self.rparams[k][self.lo:self.hi], dtype=np.float32) for k in PARAM_NAMES}
+            params = {k: torch.from_numpy(v).to(dev) for k, v in _pad_kernels(rp, self._kp).items()}
+        else:
+            params = self._params
+        axes = [torch.from_numpy(blk.render_axis(n[l], m[l])).to(dev) for l in range(d)]
+        out = None
+        if self.world_size > 1:
+            out = torch.zeros(tuple(extent) + (self.channels,), dtype=tdt, device=dev)
+        # the kernel lists of the pass behind get_reconstruction() while that reconstruction is current (the pass prunes
+        # its lists only after it has evaluated with them), the current lists otherwise
+        active = self._active
+        if self.valid and not quantized and getattr(self, "_recon_active", None) is not None:
+            active = self._recon_active
+        res = eng.render(params, active, axes, self.grid, extent, first_block=self.lo, out=out, dtype=tdt,
+                         want_argmax=want_argmax)
+        img, am = res if want_argmax else (res, None)
+        ids = None
+        if want_argmax:
+            # global kernel id = block index * K + kernel (as _assemble_one forms it); the block index of every position
+            pos = [torch.arange(extent[l], device=dev) // m[l] for l in range(d)]
+            bid = pos[0]
+            for l in range(1, d):
+                bid = bid.reshape(bid.shape + (1,)) * self.grid[l] + pos[l]
+            own = (bid >= self.lo) & (bid < self.hi)
+            am = am.to(torch.int64)
+            ids = torch.where(own & (am != 255), am + bid * self.kernels, torch.full_like(am, -1))
+            if self.world_size > 1:
+                ids = torch.where(own, ids + 1, torch.zeros_like(ids))
+        if self.world_size > 1:
+            # the positions of other ranks' blocks are zero here: the sum over ranks is the image
+            img = sdist.allreduce_sum_(img if tdt == torch.float32 else img.to(torch.int32)).to(tdt)
+            if ids is not None:
+                ids = sdist.allreduce_sum_(ids) - 1
+        if to_host:
+            img = img.cpu().numpy()
+            ids = None if ids is None else ids.cpu().numpy()
+        return (img, ids) if want_argmax else img
 
     def get_qlosses(self):
         return self.qlosses
@@ -990,6 +1074,10 @@ class SharedSmoe:
 
     def get_best_params(self):
         return self._host_params(self._best)
+
+    def render(self, *args, **kwargs):
+        raise NotImplementedError("SharedSmoe.render: global kernels with per-batch lists need a render kernel of their own; "
+                                  "use get_reconstruction()")
 
     def get_reconstruction(self):
         if not self.valid:

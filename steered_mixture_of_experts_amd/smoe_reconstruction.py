@@ -2,6 +2,10 @@
 ``Smoe(init_params=...)`` -> ONE forward pass -> reconstructed image.
 
     python -m steered_mixture_of_experts_amd.smoe_reconstruction -i IMG -r OUT -p params.pkl
+
+``--scale S`` (one value or one per axis) / ``--frames F`` (samples per block on the time axis of video input) decode the
+per-block model on another sampling grid with ``Smoe.render`` (on the device, written straight into the stitched image);
+with the defaults the output is the reference's.
 """
 import argparse
 import os
@@ -33,7 +37,8 @@ def _decode_batch_shape(image_shape, channels, batches):
 _shared_engine_factory = None      # tests put the oracle-backed engine here; None = the HIP engine
 
 
-def main(image_path, results_path, params_file, batches=1, bit_depths=(20, 18, 6, 10, 10), quant_params=False):
+def main(image_path, results_path, params_file, batches=1, bit_depths=(20, 18, 6, 10, 10), quant_params=False,
+         scale=None, frames=None):
     if len(bit_depths) != 5:
         raise ValueError("Number of bit depths must be five!")           # smoe_reconstruction.py:17-18
     orig, precision, _ = read_image(image_path)
@@ -75,6 +80,20 @@ def main(image_path, results_path, params_file, batches=1, bit_depths=(20, 18, 6
         reconstruction_path += "_{0:1d}_{1:1d}_{2:1d}_{3:1d}_{4:1d}".format(*bit_depths)
     else:
         reconstruction = smoe.get_reconstruction()
+    sc = [float(v) for v in np.atleast_1d(1.0 if scale is None else scale)]
+    if frames is not None or any(v != 1.0 for v in sc):
+        # another sampling grid: evaluate the block models there (Smoe.render); the pass above keeps loss / mse as reported
+        d = smoe.dim_domain
+        sc = sc * d if len(sc) == 1 else sc
+        if len(sc) != d:
+            raise ValueError(f"--scale takes one value or {d}")
+        if frames is not None and d != 3:
+            raise ValueError("--frames needs video input")
+        m = [max(1, int(round(v * n))) for v, n in zip(sc, smoe.batch_size_valued)]
+        if frames is not None:
+            m[2] = int(frames)
+        reconstruction = smoe.render(samples_per_block=m, quantized=with_q)
+        reconstruction_path += "_" + "x".join(str(v) for v in m)
     write_image(reconstruction, reconstruction_path, smoe.dim_domain, smoe.use_yuv, precision)
     return reconstruction, loss, mse
 
@@ -87,6 +106,9 @@ def _cli():
     parser.add_argument('-b', '--batches', type=int, default=1)
     parser.add_argument('-bd', '--bit_depths', type=int, default=[20, 18, 6, 10, 10], nargs='+')
     parser.add_argument('-qp', '--quant_params', action='store_true')
+    parser.add_argument('--scale', type=float, default=None, nargs='+',
+                        help="render at this scale (one value or one per axis; default 1 = the training lattice)")
+    parser.add_argument('--frames', type=int, default=None, help="video: samples per block on the time axis")
     args = parser.parse_args()
     main(**vars(args))
 
