@@ -265,7 +265,9 @@ int smoe_set_sampling(smoe_handle h, int32_t on);
  * For multi-GPU the host layer shards the BATCHES: every call takes the range
  * [first_batch, first_batch + num_batches) and launch-local buffers; between
  * smoe_shared_accumulate and smoe_shared_apply it all-reduces the buffer returned by
- * smoe_shared_grad_buffer (K*P+K doubles) over the ranks (RCCL sum). */
+ * smoe_shared_grad_buffer (K*P+K doubles) over the ranks (RCCL sum).
+ * Decoding: smoe_shared_forward reconstructs the training lattice as batch planes; smoe_shared_render evaluates the same
+ * model on any separable sampling grid straight into the interleaved image. */
 typedef struct smoe_shared_config {
     int32_t abi_version, device, dim;
     int32_t image_shape[SMOE_MAX_DIM];  /* pixels per axis (y, x[, t]), a multiple of batch_shape (smoe.py:239-241) */
@@ -307,6 +309,38 @@ int smoe_shared_list_words(smoe_shared_handle h);
 int smoe_shared_forward(smoe_shared_handle h, int32_t first_batch, int32_t num_batches, const float* target,
                         const smoe_params* p, float* recon, int32_t* argmax, float* loss, float* sse,
                         uint32_t* lists, int32_t update_lists, void* stream);
+
+/* Decoder of the shared-kernel mode: evaluate the ONE global kernel set on a separable sampling grid and store the samples
+ * at their place in the interleaved row-major image [E_0, E_1(, E_2), C] -- the counterpart of smoe_render for whole-image
+ * models.  No target, no loss, the lists are only read, overlap plays no part.  The sample grid is free (zoom, a finer
+ * pitch, frames between the fitted ones) and a batch may have any number of samples (smoe_shared_forward holds a batch in
+ * registers: at most 1024 / 2048 pixels).
+ *   first_batch, num_batches the batches [first_batch, first_batch + num_batches) of the handle's batch grid (row-major,
+ *                            last axis innermost: sliding_window order); a rank renders its batches into a full-size buffer
+ *   p                        the global kernels, as in smoe_shared_forward.  A kernel counts when it is listed and its
+ *                            (fake-quantised) prior is > 0; the parameters go through the handle's fake quantisation
+ *                            (quantize_pis, quantization_mode 2, mode 3 with the IMAGE-wide ranges of THIS call's parameters,
+ *                            the centre grid of smoe_shared_set_center_grid) exactly as in smoe_shared_forward
+ *   lists                    launch-local [num_batches, KW] bitmaps (row 0 = batch first_batch), only read; NULL = every
+ *                            kernel.  A sample is evaluated with the list of the batch that owns its position
+ *   axis_coords[l], samples[l]  samples[l] = samples per BATCH on axis l; the image has E_l = grid_l * samples[l] samples
+ *                            (grid_l = image_shape[l] / batch_shape[l]) and axis_coords[l] is a DEVICE table of E_l fp32
+ *                            coordinates in image units (the unit in which the training lattice is
+ *                            linspace(0, 1, image_shape[l])).  Position j_l belongs to batch index j_l / samples[l] on that
+ *                            axis.  Values outside [0, 1] are legal.  Offsets into the image are 64-bit
+ *   image, image_format      SMOE_IMAGE_F32: the lattice values smoe_shared_forward writes into recon -- bit-identical to
+ *                            it on the training lattice (samples = batch_shape, axis_coords[l] = linspace(0, 1,
+ *                            image_shape[l]) in fp32) for the same handle state, parameters and lists;
+ *                            SMOE_IMAGE_U8: the lattice indices (precision <= 8)
+ *   argmax                   [E_0, E_1(, E_2)] int32 or NULL: GLOBAL kernel id of the first maximum among the kernels with
+ *                            influence on the sample, -1 where none has (smoe_shared_forward replaces such pixels by a
+ *                            batch-wide choice made on the training lattice; a render grid has none, so the -1 stays)
+ * Entries [dim .. 2] of the arrays are ignored.  Only positions owned by the rendered batches are written.  Stores are
+ * 16-byte wide when image / argmax are 16-byte aligned.  The result does not depend on how the launch spreads a batch
+ * over workgroups (few batches are split; environment SMOE_SHARED_RENDER_SPLIT=n forces n workgroups per batch). */
+int smoe_shared_render(smoe_shared_handle h, int32_t first_batch, int32_t num_batches, const smoe_params* p,
+                       const uint32_t* lists, const float* const axis_coords[3], const int32_t samples[3],
+                       void* image, int32_t image_format, int32_t* argmax, void* stream);
 
 /* run_batched(train=True) minus train_op: forward + tf.gradients of the batches, accumulated into
  * the handle's gradient buffer (accum_ops, smoe.py:1150); kernel lists pruned (smoe.py:1763-1766).

@@ -30,7 +30,7 @@ EXPORTS = (
     "smoe_shared_forward", "smoe_shared_accumulate", "smoe_shared_apply", "smoe_shared_grad_buffer",
     "smoe_shared_fit", "smoe_shared_update_kernel_list", "smoe_shared_set_loss_weights",
     "smoe_set_center_grid", "smoe_shared_set_center_grid", "smoe_set_total_blocks", "smoe_padded_kernels_full", "smoe_shared_discard", "smoe_set_sampling",
-    "smoe_render",
+    "smoe_render", "smoe_shared_render",
 )
 
 
@@ -121,6 +121,8 @@ def load() -> C.CDLL:
     lib.smoe_shared_num_batches.argtypes = [vp]
     lib.smoe_shared_list_words.argtypes = [vp]
     lib.smoe_shared_forward.argtypes = [vp, i32, i32, fp, C.POINTER(SmoeParams), fp, fp, fp, fp, fp, i32, vp]
+    lib.smoe_shared_render.argtypes = [vp, i32, i32, C.POINTER(SmoeParams), fp, C.POINTER(C.c_void_p), C.POINTER(C.c_int32),
+                                       fp, i32, fp, vp]
     lib.smoe_shared_accumulate.argtypes = [vp, i32, i32, fp, C.POINTER(SmoeParams), fp, fp, fp, vp]
     lib.smoe_shared_apply.argtypes = [vp, C.POINTER(SmoeParams), C.POINTER(SmoeAdamState), vp]
     lib.smoe_shared_grad_buffer.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]

@@ -1199,6 +1199,57 @@ int smoe_shared_forward(smoe_shared_handle h, int32_t first_batch, int32_t num_b
     return SMOE_OK;
 }
 
+int smoe_shared_render(smoe_shared_handle h, int32_t first_batch, int32_t num_batches, const smoe_params* p,
+                       const uint32_t* lists, const float* const axis_coords[3], const int32_t samples[3],
+                       void* image, int32_t image_format, int32_t* argmax, void* stream) {
+    if (!h) return fail(SMOE_ERR_INVALID, "smoe_shared_render: null handle");
+    int rc = check_range(h, first_batch, num_batches, "smoe_shared_render");
+    if (rc) return rc;
+    if (!params_ok(p)) return fail(SMOE_ERR_INVALID, "smoe_shared_render: p (all six parameter tensors) is required");
+    if (!image) return fail(SMOE_ERR_INVALID, "smoe_shared_render: image is required");
+    if (!axis_coords || !samples) return fail(SMOE_ERR_INVALID, "smoe_shared_render: axis_coords and samples are required");
+    if (image_format != SMOE_IMAGE_F32 && image_format != SMOE_IMAGE_U8)
+        return fail(SMOE_ERR_INVALID, "smoe_shared_render: image_format must be SMOE_IMAGE_F32 or SMOE_IMAGE_U8");
+    const int D = h->cfg.dim;
+    for (int l = 0; l < D; ++l) {
+        const std::string ax = "[" + std::to_string(l) + "]";
+        if (!axis_coords[l]) return fail(SMOE_ERR_INVALID, "smoe_shared_render: axis_coords" + ax + " is null");
+        if (samples[l] < 1) return fail(SMOE_ERR_INVALID, "smoe_shared_render: samples" + ax + " must be >= 1");
+    }
+    if (image_format == SMOE_IMAGE_U8 && h->cfg.precision > 8)
+        return fail(SMOE_ERR_INVALID, "smoe_shared_render: SMOE_IMAGE_U8 needs precision <= 8");
+    if (num_batches == 0) return SMOE_OK;
+    rc = shared_check_abort(h, "smoe_shared_render");
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(h->cfg.device), "hipSetDevice");
+    smoe::SharedRenderArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.p = *p; a.lists = lists;
+    for (int l = 0; l < SMOE_MAX_DIM; ++l) {
+        a.ax[l] = (l < D) ? axis_coords[l] : nullptr;
+        a.m[l] = (l < D) ? samples[l] : 1;
+        a.grid[l] = (l < D) ? h->grid[l] : 1;
+        a.ext[l] = (long long)a.grid[l] * a.m[l];
+    }
+    a.b0 = first_batch; a.nb = num_batches; a.K = h->cfg.kernels; a.KW = h->KW;
+    a.image = image; a.fmt = image_format; a.argmax = argmax;
+    a.vec_img = ((uintptr_t)image % 16 == 0) ? 1 : 0;
+    a.vec_arg = ((uintptr_t)argmax % 16 == 0) ? 1 : 0;
+    a.qrng = h->d_qrng; a.mus_grid = h->mus_grid;
+    a.kc = h->kc;
+    // SMOE_SHARED_RENDER_SPLIT=n: n workgroups per batch instead of the automatic choice (tuning / test hook; the image does
+    // not depend on it)
+    int split_hint = 0;
+    if (const char* v = std::getenv("SMOE_SHARED_RENDER_SPLIT")) split_hint = std::atoi(v);
+    HIP_TRY(refresh_ranges(h, p, (hipStream_t)stream), "smoe_shared_render ranges");
+    {
+        const hipError_t e = smoe::launch_shared_render(a, D, h->cfg.channels, h->num_cus, split_hint, (hipStream_t)stream);
+        if (e == hipErrorNotSupported) return fail(SMOE_ERR_UNSUPPORTED, "smoe_shared_render: more than 2^30 samples per batch");
+        if (e != hipSuccess) return fail_hip(e, "smoe_shared_render launch");
+    }
+    return SMOE_OK;
+}
+
 // gather: sum the batches' rows into the gradient buffer right away (what smoe_shared_grad_buffer hands out for the
 // all-reduce); smoe_shared_fit leaves it to the step kernel (one launch less per iteration)
 static int shared_accumulate_impl(smoe_shared_handle h, int32_t first_batch, int32_t num_batches, const float* target,

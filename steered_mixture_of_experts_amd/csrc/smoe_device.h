@@ -198,6 +198,26 @@ struct SharedArgs {
     uint32_t epoch;
 };
 
+// smoe_shared_render (smoe_shared_render.hip.h): evaluate the batches [b0, b0 + nb) of the image on a separable sample grid
+// with their kernel lists and store the samples into the interleaved image.  The launcher fills tiles / split.
+struct SharedRenderArgs {
+    smoe_params p;            // global kernels [K,...]
+    const uint32_t* lists;    // launch-local [nb][KW] bitmaps (row 0 = batch b0), only read; null = every kernel
+    const float* ax[SMOE_MAX_DIM];   // per-axis sample coordinates of the WHOLE image [E_l], image units
+    int m[SMOE_MAX_DIM];      // samples per batch and axis
+    int grid[SMOE_MAX_DIM];   // batches per axis
+    long long ext[SMOE_MAX_DIM];     // E_l = grid_l * m_l
+    int b0, nb, K, KW;
+    void* image;              // [E_0, E_1(, E_2), C] float32 or uint8
+    int fmt;                  // SMOE_IMAGE_F32 / SMOE_IMAGE_U8
+    int32_t* argmax;          // [E_0, E_1(, E_2)] global kernel ids, -1 = no kernel has influence; or null
+    int vec_img, vec_arg;     // the plane's base is 16-byte aligned: vector stores
+    int tiles, split;         // tiles of SR_TILE samples per batch, workgroups per batch
+    const float* qrng;        // as in SharedArgs
+    const float* mus_grid;    // as in SharedArgs
+    KernelConsts kc;
+};
+
 // Per-kernel sum over the batches of the current pass, in a fixed order (lane = batch mod 64 ascending, then a butterfly
 // over the lanes): racc[k][PK] and nact[k] are OVERWRITTEN -- bit-identical from run to run and for every split of the
 // batches of a rank over smoe_shared_accumulate calls.
@@ -271,6 +291,9 @@ hipError_t launch_shared_gather(const SharedGatherArgs& g, hipStream_t st);
 hipError_t launch_shared_fit(const SharedFitArgs& f, int D, int C, int num_cus, hipStream_t st);
 hipError_t launch_shared_readmit(const SharedReadmitArgs& a, int D, hipStream_t st);
 hipError_t launch_shared_ranges(const SharedRangesArgs& a, int D, int C, hipStream_t st);
+// split_hint > 0: workgroups per batch (test / tuning hook); 0: chosen from nb and num_cus.  hipErrorNotSupported: more than
+// 2^30 samples per batch
+hipError_t launch_shared_render(const SharedRenderArgs& a, int D, int C, int num_cus, int split_hint, hipStream_t st);
 
 const Variant* variants(int* count);
 hipError_t launch_readmit(const ReadmitArgs& a, int D, hipStream_t st);

@@ -15,6 +15,7 @@
 #include "smoe_device.h"
 #include "smoe_ssim.hip.h"
 #include "smoe_fq.hip.h"
+#include "smoe_render.hip.h"        // render_store_piece / store_stream (smoe_shared_render.hip.h)
 
 namespace smoe {
 
@@ -136,6 +137,70 @@ __device__ __forceinline__ float fexp2(float x) { return __builtin_amdgcn_exp2f(
 
 }  // namespace
 
+// Staged record of kernel k (derived quantities, smoe.py:732-733,809-819): SL<D, C>::SP floats at r.  One definition for
+// the pass (shared_pass_body) and the decoder (smoe_shared_render.hip.h): the same record gives the same sample bit for bit.
+template <int D, int C, bool IC, bool COH>
+__device__ __forceinline__ void shared_stage_record(const smoe_params& p, const KernelConsts& kc, const float* qrng,
+                                                    const float* mus_grid, const int k, float* r) {
+    using L = SL<D, C>;
+    float det = 1.0f;
+    float A[D][D];
+#pragma unroll
+    for (int l = 0; l < D; ++l)
+#pragma unroll
+        for (int m = 0; m <= l; ++m) {
+            A[l][m] = fqt((l == m) ? gload<COH>(&p.A_diagonal[((size_t)k * D + l) * D + m]) : gload<COH>(&p.A_corr[((size_t)k * D + l) * D + m]), kc, qrng, (l == m) ? 0 : 1);
+            if (l == m) det *= A[l][m];
+            // train_inverse_cov: the coefficients c_lm of r^T A' r over l >= m, A' = SQ^2 A (smoe.py:734-735,791-793)
+            r[L::O_AS + tri(l, m)] = IC ? ((l == m) ? SQ * SQ : 2.0f * SQ * SQ) * A[l][m] : SQ * A[l][m];
+        }
+#pragma unroll
+    for (int m = 0; m < D; ++m) {
+        float cz = 0.0f;
+        if (IC) {
+            cz = mu_graph<D, COH>(p.musX, mus_grid, kc, qrng, k, m);   // the centre itself: r = x - mu per pixel
+        } else {
+#pragma unroll
+            for (int l = m; l < D; ++l) cz = fmaf(mu_graph<D, COH>(p.musX, mus_grid, kc, qrng, k, l), SQ * A[l][m], cz);
+        }
+        r[L::O_CZ + m] = cz;
+    }
+    const float nq = kc.use_det ? det / kc.n_dis : 1.0f;
+    r[L::O_COEF] = nq * fqv(gload<COH>(&p.pis[k]), kc, 3);
+#pragma unroll
+    for (int c = 0; c < C; ++c) r[L::O_NU + c] = fqt(gload<COH>(&p.nu_e[(size_t)k * C + c]), kc, qrng, 3);
+#pragma unroll
+    for (int i = 0; i < D * C; ++i)
+        r[L::O_GA + i] = (kc.train_gammas && !(kc.only_y_gamma && (i % C) != 0)) ? fqt(gload<COH>(&p.gamma_e[(size_t)k * D * C + i]), kc, qrng, 4) : 0.0f;
+}
+
+// g_k(x) * 1 and z' for one pixel, from the staged record
+template <int D, int C, bool IC>
+__device__ __forceinline__ float shared_gate(const float* r, const float (&xx)[D], float (&z)[D]) {
+    using L = SL<D, C>;
+    float maha = 0.0f;
+    if (IC) {                                  // z := r = x - mu ; maha' = sum_{l>=m} c_lm r_l r_m
+#pragma unroll
+        for (int l = 0; l < D; ++l) {
+            z[l] = xx[l] - r[L::O_CZ + l];
+            float tq = 0.0f;
+#pragma unroll
+            for (int m = 0; m <= l; ++m) tq = fmaf(r[L::O_AS + tri(l, m)], z[m], tq);
+            maha = fmaf(tq, z[l], maha);
+        }
+        return r[L::O_COEF] * fexp2(-maha);
+    }
+#pragma unroll
+    for (int m = 0; m < D; ++m) {
+        float zz = -r[L::O_CZ + m];
+#pragma unroll
+        for (int l = D - 1; l >= m; --l) zz = fmaf(xx[l], r[L::O_AS + tri(l, m)], zz);
+        z[m] = zz;
+        maha = (m == 0) ? zz * zz : fmaf(zz, zz, maha);
+    }
+    return r[L::O_COEF] * fexp2(-maha);
+}
+
 // ---------------------------------------------------------------------------------------------
 // one pass over all batches
 // ---------------------------------------------------------------------------------------------
@@ -233,66 +298,12 @@ __device__ __forceinline__ void shared_pass_body(const SharedArgs& a, const int 
         if (c0 == staged_c0) return;
         staged_c0 = c0;
         __syncthreads();
-        if (tid < n) {
-            const int k = s_list[c0 + tid];
-            float* r = s_par + tid * L::SP;
-            float det = 1.0f;
-            float A[D][D];
-#pragma unroll
-            for (int l = 0; l < D; ++l)
-#pragma unroll
-                for (int m = 0; m <= l; ++m) {
-                    A[l][m] = fqt((l == m) ? gload<COH>(&a.p.A_diagonal[((size_t)k * D + l) * D + m]) : gload<COH>(&a.p.A_corr[((size_t)k * D + l) * D + m]), a.kc, a.qrng, (l == m) ? 0 : 1);
-                    if (l == m) det *= A[l][m];
-                    // train_inverse_cov: the coefficients c_lm of r^T A' r over l >= m, A' = SQ^2 A (smoe.py:734-735,791-793)
-                    r[L::O_AS + tri(l, m)] = ic ? ((l == m) ? SQ * SQ : 2.0f * SQ * SQ) * A[l][m] : SQ * A[l][m];
-                }
-#pragma unroll
-            for (int m = 0; m < D; ++m) {
-                float cz = 0.0f;
-                if (ic) {
-                    cz = mu_graph<D, COH>(a.p.musX, a.mus_grid, a.kc, a.qrng, k, m);   // the centre itself: r = x - mu per pixel
-                } else {
-#pragma unroll
-                    for (int l = m; l < D; ++l) cz = fmaf(mu_graph<D, COH>(a.p.musX, a.mus_grid, a.kc, a.qrng, k, l), SQ * A[l][m], cz);
-                }
-                r[L::O_CZ + m] = cz;
-            }
-            const float nq = a.kc.use_det ? det / a.kc.n_dis : 1.0f;
-            r[L::O_COEF] = nq * fqv(gload<COH>(&a.p.pis[k]), a.kc, 3);
-#pragma unroll
-            for (int c = 0; c < C; ++c) r[L::O_NU + c] = fqt(gload<COH>(&a.p.nu_e[(size_t)k * C + c]), a.kc, a.qrng, 3);
-#pragma unroll
-            for (int i = 0; i < D * C; ++i)
-                r[L::O_GA + i] = (a.kc.train_gammas && !(a.kc.only_y_gamma && (i % C) != 0)) ? fqt(gload<COH>(&a.p.gamma_e[(size_t)k * D * C + i]), a.kc, a.qrng, 4) : 0.0f;
-        }
+        if (tid < n) shared_stage_record<D, C, IC, COH>(a.p, a.kc, a.qrng, a.mus_grid, s_list[c0 + tid], s_par + tid * L::SP);
         __syncthreads();
     };
 
     // g_k(x) * 1 and z' for one pixel
-    auto gate = [&](const float* r, const float (&xx)[D], float (&z)[D]) -> float {
-        float maha = 0.0f;
-        if (ic) {                                  // z := r = x - mu ; maha' = sum_{l>=m} c_lm r_l r_m
-#pragma unroll
-            for (int l = 0; l < D; ++l) {
-                z[l] = xx[l] - r[L::O_CZ + l];
-                float tq = 0.0f;
-#pragma unroll
-                for (int m = 0; m <= l; ++m) tq = fmaf(r[L::O_AS + tri(l, m)], z[m], tq);
-                maha = fmaf(tq, z[l], maha);
-            }
-            return r[L::O_COEF] * fexp2(-maha);
-        }
-#pragma unroll
-        for (int m = 0; m < D; ++m) {
-            float zz = -r[L::O_CZ + m];
-#pragma unroll
-            for (int l = D - 1; l >= m; --l) zz = fmaf(xx[l], r[L::O_AS + tri(l, m)], zz);
-            z[m] = zz;
-            maha = (m == 0) ? zz * zz : fmaf(zz, zz, maha);
-        }
-        return r[L::O_COEF] * fexp2(-maha);
-    };
+    auto gate = [&](const float* r, const float (&xx)[D], float (&z)[D]) -> float { return shared_gate<D, C, IC>(r, xx, z); };
 
     // ---- 2. sweep A: gate normaliser (smoe.py:819-821) ---------------------------------------------
     float S[PXL];
@@ -1126,6 +1137,13 @@ __global__ void shared_readmit_kernel(SharedReadmitArgs a) {
     }
     if (near) atomicOr(&a.lists[(size_t)b * a.KW + (k >> 5)], 1u << (k & 31));
 }
+
+}  // namespace smoe
+
+// the decoder of this mode (shared_render_kernel, launch_shared_render)
+#include "smoe_shared_render.hip.h"
+
+namespace smoe {
 
 // ---------------------------------------------------------------------------------------------
 // launchers

@@ -471,6 +471,54 @@ class SharedEngine:
                                                 int(update_lists), self._stream()))
         return out
 
+    def render(self, params, lists, axes, samples, first_batch=0, out=None, dtype=torch.float32, want_argmax=False,
+               num_batches=None):
+        """Decode: evaluate the batches ``[first_batch, first_batch + nb)`` on the separable sample grid ``axes`` (one
+        float32 device table per IMAGE axis with ``grid_l * samples[l]`` coordinates in image units) into the interleaved
+        image ``[*E, C]``, ``E_l = grid_l * samples[l]`` (include/smoe_hip.h: smoe_shared_render).  ``lists`` [nb, KW] int32
+        (row 0 = batch ``first_batch``, only read) or None: every kernel, ``nb`` then comes from ``num_batches`` (default:
+        all batches from ``first_batch`` on).  ``out``: a full-size image to render into (only the positions of the
+        rendered batches are written); otherwise a new one, zero-filled where this call renders only a part.  Returns the
+        image, with ``want_argmax`` also the int32 map ``[*E]`` of global kernel ids (-1: no kernel has influence on the
+        sample; -1 as well where no batch was rendered)."""
+        d, Cc = self.cfg.dim, self.cfg.channels
+        if dtype not in (torch.float32, torch.uint8):
+            raise ValueError("render: dtype must be torch.float32 or torch.uint8")
+        if len(axes) != d or len(samples) != d:
+            raise ValueError(f"render: axes and samples need {d} entries")
+        samples = [int(m) for m in samples]
+        if min(samples) < 1:
+            raise ValueError("render: at least one sample per batch and axis")
+        grid = [int(s) // int(b) for s, b in zip(self.cfg.image_shape, self.cfg.batch_shape)]
+        extent = [g * m for g, m in zip(grid, samples)]
+        for t, e in zip(axes, extent):
+            if t.dim() != 1 or t.numel() != e or t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"render: every axis table must be a contiguous 1-d float32 tensor on {self.device} with "
+                                 f"grid * samples entries ({extent})")
+        if lists is not None:
+            nb = int(lists.shape[0])
+            if (tuple(lists.shape) != (nb, self.list_words) or lists.dtype != torch.int32 or not lists.is_contiguous()
+                    or lists.device != self.device):
+                raise ValueError(f"render: lists must be a contiguous int32 [nb, {self.list_words}] tensor on {self.device}")
+        else:
+            nb = self.num_batches - int(first_batch) if num_batches is None else int(num_batches)
+        if first_batch < 0 or nb < 0 or first_batch + nb > self.num_batches:
+            raise ValueError("render: batch range out of bounds")
+        shape = tuple(extent) + (Cc,)
+        if out is None:
+            out = (torch.empty if nb == self.num_batches else torch.zeros)(shape, dtype=dtype, device=self.device)
+        elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"render: out must be a contiguous {dtype} tensor {shape} on {self.device}")
+        am = torch.full(tuple(extent), -1, dtype=torch.int32, device=self.device) if want_argmax else None
+        if nb > 0:
+            cp = self._cparams(params)
+            tabs = (C.c_void_p * 3)(*([t.data_ptr() for t in axes] + [None] * (3 - d)))
+            m3 = (C.c_int32 * 3)(*(samples + [1] * (3 - d)))
+            fmt = _lib.SMOE_IMAGE_U8 if dtype == torch.uint8 else _lib.SMOE_IMAGE_F32
+            _lib.check(self.lib.smoe_shared_render(self._h, int(first_batch), nb, C.byref(cp), _ptr(lists), tabs, m3,
+                                                   _ptr(out), fmt, _ptr(am), self._stream()))
+        return (out, am) if want_argmax else out
+
     def accumulate(self, target, params, lists, first_batch=0, loss_out=None, sse_out=None):
         nb = lists.shape[0]
         self._check_target(target, nb)

@@ -915,6 +915,7 @@ class SharedSmoe:
         self.best_loss, self.best_mse = None, []
         self.iter = iter_offset
         self.valid = False
+        self._recon_lists = self._qrecon_lists = None
         self.reconstruction_image = self.weight_matrix_argmax = None
         self.qparams = self.rparams = None                                # quantizer.py products (leading axis 1 = the model)
         self.qreconstruction_image = None
@@ -998,6 +999,7 @@ class SharedSmoe:
             out = eng.forward(self._target, rp, self._lists, first_batch=self.lo, want_recon=update_reconstruction,
                               want_argmax=False, update_lists=False)
             if update_reconstruction:
+                self._qrecon_lists = self._lists.clone()    # what this pass evaluated with (render(quantized=True))
                 bs, d = self.batch_size_valued, self.dim_domain
                 rec = sdist.allgather_blocks(blk.from_planar(out["recon"].cpu().numpy(), bs), self.num_batches)
                 self.qreconstruction_image = blk.blocks_to_image(rec, self.image.shape[:d], bs)
@@ -1014,6 +1016,8 @@ class SharedSmoe:
                 sdist.allreduce_sum_(eng.grad_buffer())                    # the gradient exchange of the pass
             eng.apply(self._params, self._state)
         else:
+            if update_reconstruction:
+                self._recon_lists = self._lists.clone()     # what this pass evaluates with, before it prunes (render)
             out = eng.forward(self._target, self._params, self._lists, first_batch=self.lo,
                               want_recon=update_reconstruction, want_argmax=update_reconstruction)
             loss, sse = out["loss"], out["sse"]
@@ -1075,9 +1079,92 @@ class SharedSmoe:
     def get_best_params(self):
         return self._host_params(self._best)
 
-    def render(self, *args, **kwargs):
-        raise NotImplementedError("SharedSmoe.render: global kernels with per-batch lists need a render kernel of their own; "
-                                  "use get_reconstruction()")
+    def render(self, scale=None, samples_per_block=None, dtype=np.float32, quantized=False, want_argmax=False,
+               to_host=True, use_lists=True):
+        """Decode the fitted whole-image model on another sampling grid, on the device (the engine's ``render``).  The
+        model is ONE continuous function over the image domain -- no block seams -- so zooming, a finer pitch or frames
+        between the fitted ones are "evaluate the same model somewhere else"; no pixel is interpolated.
+        ``scale``: a number or one per axis, ``m_l = round(scale_l * n_l)`` samples per batch (at least 1, ``n`` =
+        ``batch_size_valued``); ``samples_per_block``: the ``m_l`` themselves (a number or one per axis); neither: the
+        training lattice.  Output extent ``E_l = grid_l * m_l`` (the image is a multiple of the batch: nothing to crop),
+        layout ``[*E, C]`` as ``get_reconstruction()``; ``dtype`` float32 (lattice values) or uint8 (lattice indices).
+        Sample positions: ``blocks.render_axis(image.shape[l], E_l)`` on the IMAGE axis -- ``E_l == image.shape[l]`` is the
+        training lattice itself, otherwise cell centres over the image's pixel footprint; sample ``j`` lies in the
+        footprint of batch ``j // m_l`` and is evaluated with that batch's kernel list.
+        ``quantized``: render ``rparams`` (what ``get_qreconstruction`` evaluates).  ``want_argmax``: also the map of
+        global kernel ids ``[*E]`` (int64; -1 where no kernel has influence on the sample).  ``to_host=False`` returns
+        device tensors.
+        Lists: the ones the pass behind ``get_reconstruction()`` (``quantized``: ``get_qreconstruction()``) evaluated with
+        while that reconstruction is current (a pass prunes the lists only after it has evaluated with them), the current
+        ones otherwise.  A kernel that was pruned
+        from a batch because it had no influence on the batch's PIXELS may be missing at an in-between sample near the
+        batch's edge.  ``use_lists=False`` passes no lists: every kernel with a positive prior, everywhere -- slower, and
+        free of the list boundaries.  (It is not the same function even on the training lattice: a pruned kernel's masked
+        weight was zero, but its gate still sat in the normaliser of the pass that pruned it.)
+        Several ranks: every rank renders its batches and the images are summed; the result is the same on every rank
+        and for every number of ranks."""
+        d, n = self.dim_domain, self.batch_size_valued
+        if scale is not None and samples_per_block is not None:
+            raise ValueError("render: give scale or samples_per_block, not both")
+        if samples_per_block is not None:
+            spb = list(np.atleast_1d(samples_per_block))
+            spb = spb * d if len(spb) == 1 else spb
+            if len(spb) != d:
+                raise ValueError(f"render: samples_per_block needs one value or {d}")
+            m = [int(v) for v in spb]
+        else:
+            sc = list(np.atleast_1d(1 if scale is None else scale))
+            sc = sc * d if len(sc) == 1 else sc
+            if len(sc) != d:
+                raise ValueError(f"render: scale needs one value or {d}")
+            m = [max(1, int(round(float(v) * nl))) for v, nl in zip(sc, n)]
+        if min(m) < 1:
+            raise ValueError("render: at least one sample per batch and axis")
+        npdt = np.dtype(dtype)
+        if npdt not in (np.dtype(np.float32), np.dtype(np.uint8)):
+            raise ValueError("render: dtype must be float32 or uint8")
+        tdt = torch.uint8 if npdt == np.dtype(np.uint8) else torch.float32
+        eng = self._engine
+        if not hasattr(eng, "render"):
+            raise NotImplementedError("this engine has no render()")
+        dev = eng.device
+        grid = [int(self.image.shape[l]) // n[l] for l in range(d)]
+        extent = [grid[l] * m[l] for l in range(d)]
+        if quantized:
+            assert self.rparams is not None, "quantize_params + rescaler first (smoe.py:1499-1501)"
+            params = {k: torch.from_numpy(np.ascontiguousarray(self.rparams[k][0], dtype=np.float32)).to(dev) for k in PARAM_NAMES}
+        else:
+            params = self._params
+        axes = [torch.from_numpy(blk.render_axis(int(self.image.shape[l]), extent[l])).to(dev) for l in range(d)]
+        lists = None
+        if use_lists:
+            lists = self._lists
+            if quantized and self.qvalid and getattr(self, "_qrecon_lists", None) is not None:
+                lists = self._qrecon_lists
+            elif not quantized and self.valid and getattr(self, "_recon_lists", None) is not None:
+                lists = self._recon_lists
+        out = None
+        if self.world_size > 1:
+            out = torch.zeros(tuple(extent) + (self.image.shape[-1],), dtype=tdt, device=dev)
+        res = eng.render(params, lists, axes, m, first_batch=self.lo, out=out, dtype=tdt, want_argmax=want_argmax,
+                         num_batches=self.hi - self.lo)
+        img, ids = res if want_argmax else (res, None)
+        if ids is not None:
+            ids = ids.to(torch.int64)
+        if self.world_size > 1:
+            # the positions of other ranks' batches are zero here: the sum over ranks is the image (ids shifted by one)
+            img = sdist.allreduce_sum_(img if tdt == torch.float32 else img.to(torch.int32)).to(tdt)
+            if ids is not None:
+                pos = [torch.arange(extent[l], device=dev) // m[l] for l in range(d)]
+                bid = pos[0]
+                for l in range(1, d):
+                    bid = bid.reshape(bid.shape + (1,)) * grid[l] + pos[l]
+                own = (bid >= self.lo) & (bid < self.hi)
+                ids = sdist.allreduce_sum_(torch.where(own, ids + 1, torch.zeros_like(ids))) - 1
+        if to_host:
+            img = img.cpu().numpy()
+            ids = None if ids is None else ids.cpu().numpy()
+        return (img, ids) if want_argmax else img
 
     def get_reconstruction(self):
         if not self.valid:

@@ -4,8 +4,8 @@
     python -m steered_mixture_of_experts_amd.smoe_reconstruction -i IMG -r OUT -p params.pkl
 
 ``--scale S`` (one value or one per axis) / ``--frames F`` (samples per block on the time axis of video input) decode the
-per-block model on another sampling grid with ``Smoe.render`` (on the device, written straight into the stitched image);
-with the defaults the output is the reference's.
+model on another sampling grid with ``Smoe.render`` / ``SharedSmoe.render`` (per-block and whole-image pickles alike; on
+the device, written straight into the stitched image); with the defaults the output is the reference's.
 """
 import argparse
 import os
@@ -82,7 +82,8 @@ def main(image_path, results_path, params_file, batches=1, bit_depths=(20, 18, 6
         reconstruction = smoe.get_reconstruction()
     sc = [float(v) for v in np.atleast_1d(1.0 if scale is None else scale)]
     if frames is not None or any(v != 1.0 for v in sc):
-        # another sampling grid: evaluate the block models there (Smoe.render); the pass above keeps loss / mse as reported
+        # another sampling grid: evaluate the model there (Smoe.render / SharedSmoe.render); the pass above keeps loss / mse
+        # as reported
         d = smoe.dim_domain
         sc = sc * d if len(sc) == 1 else sc
         if len(sc) != d:
