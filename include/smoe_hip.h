@@ -158,7 +158,11 @@ int smoe_forward(smoe_handle h, int32_t num_blocks, const float* target, const f
  * run_batched(train=True) = zero accumulators (1613), forward + tf.gradients (1702,1148),
  * kernel-list prune (1763-1766), one ApplyAdam per group (1788,1173-1193), and the
  * per-iteration divergence test (1565-1570, per block).
- *   p, s      in/out           loss_last/sse_last [B]: values of the LAST train pass (may be NULL)
+ *   p, s      in/out           loss_last/sse_last [B]: values of the LAST train pass (may be NULL).  A frozen block makes
+ *                              no pass: its entries keep the values of its last one, and are left as the caller passed
+ *                              them if it was frozen when the call started -- pass the same (initialised) arrays to
+ *                              consecutive calls and they read the same however the iterations are split over calls.
+ *                              The entries of such a block are NOT written: arrays passed uninitialised hold garbage there
  *   active    [B] in/out       diverged [B] uint32 in/out (non-zero = block frozen), may be NULL
  *   loss0     [B] iteration-0 loss for the blow-up test, or NULL (NaN test only) */
 int smoe_fit(smoe_handle h, int32_t num_blocks, const float* target, const float* loss_w,
@@ -216,6 +220,14 @@ int smoe_render(smoe_handle h, int32_t first_block, int32_t num_blocks, const sm
 
 /* Name of the kernel variant smoe_fit would launch for num_blocks (diagnostics / profiles). */
 const char* smoe_fit_variant(smoe_handle h, int32_t num_blocks);
+
+/* Name of the kernel the LAST smoe_fit call of this handle launched ("" before the first launch): the variant the call
+ * chose with ITS arguments -- smoe_fit_variant asks without loss weights, and with them the LDS a block needs grows, so
+ * the duo / team rules and the LDS-fit fallback can settle on another kernel -- followed by the tiling suffix
+ * (_duo64w2, _team16wN, _pair = one block on both wavefronts of the 64-lane kernel), the graph instantiation
+ * (+ssim, +quant, +ic) and the loss-weight marks (+lw: loss_w was passed; +sample: and taken as a pixel sub-sample).
+ * Diagnostics / tests: lets a caller assert which kernel a result came from. */
+const char* smoe_last_fit_variant(smoe_handle h);
 
 /* Resident wavefronts per CU the runtime grants smoe_fit's kernel for num_blocks (diagnostics). */
 int smoe_fit_occupancy(smoe_handle h, int32_t num_blocks);

@@ -1,5 +1,10 @@
 """Randomised GPU-vs-oracle sweep over block shapes and option combinations: one evaluation pass and one fit step per
-case, the tolerances of tests/test_gpu_parity.py.  Prints every failing case; exit code = number of failures."""
+case, the tolerances of tests/test_gpu_parity.py.  Prints every failing case; exit code = number of failures.
+
+Every case also draws -- from a generator of its own, seeded by the case index, so that the shapes and options of a sweep do
+not depend on these -- a loss-weight kind (none / padding mask / fractional / pixel sub-sample), the state the fit step starts
+from (fresh slots, or "teacher-forced": the slots, beta powers and lists the fp32 restatement reached after seven iterations,
+tests/step_parity.py) and whether the kernel list is partial."""
 import os
 import sys
 import traceback
@@ -15,6 +20,38 @@ from test_gpu_parity import _engine, _mask_to_bits, _planar, _setup, _to_dev, _t
 
 STATS = []
 QKW = dict(bit_depths=(14, 12, 8, 10, 10), lower_bounds=(-60, -.3, -1, 0, -4), upper_bounds=(60, 1.3, 2, 2, 4))
+WARMUP = 7          # iterations of the fp32 restatement behind a "teacher-forced" state (tests/step_parity.py takes it from here)
+
+
+def make_weights(kind, shape, B, rng, corner=2):
+    """(loss_w (B,N) float32 or None, fed (B,N) bool or None) of one weight kind; tests/step_parity.py takes it from here."""
+    N = int(np.prod(shape))
+    if kind == "none":
+        return None, None
+    if kind == "frac":
+        return rng.uniform(0.0, 1.0, size=(B, N)).astype(np.float32), None
+    if kind == "pad":
+        # what zero-padding a ragged image leaves in its border blocks: a box of valid pixels, cut in the last rows / columns /
+        # frames; block 0 all valid, block 1 wholly in the padding
+        lw = np.zeros((B,) + tuple(shape), np.float32)
+        for b in range(B):
+            ext = [s if rng.random() < 0.35 else int(rng.integers(1, s + 1)) for s in shape]
+            if b == 0:
+                ext = list(shape)
+            if b != 1:
+                lw[(b,) + tuple(slice(0, e) for e in ext)] = 1.0
+        return lw.reshape(B, N), None
+    if kind == "sample":
+        # N / n on the drawn pixels; one block's sample avoids the corner around kernel 0's centre
+        fed = np.zeros((B, N), bool)
+        for b in range(B):
+            n = int(rng.integers(max(N // 4, 1), max(3 * N // 4, 2)))
+            fed[b, rng.choice(N, size=n, replace=False)] = True
+        x = o.block_coords(shape)
+        fed[corner, (x[:, 0] < 0.56) & (x[:, 1] < 0.56)] = False
+        n = fed.sum(axis=1, keepdims=True)
+        return np.where(fed, N / n, 0.0).astype(np.float32), fed
+    raise ValueError(kind)
 
 
 def one_case(rng, idx):
@@ -61,7 +98,11 @@ def one_case(rng, idx):
     tiling = int(rng.choice([0, 16, 32, 64, 128]))
     if os.environ.get('FUZZ_TILING'):
         tiling = int(os.environ['FUZZ_TILING'])
-    desc = dict(idx=idx, shape=shape, C=C, kpd=kpd, yuv=yuv, B=B, tiling=tiling, **kw)
+    rng2 = np.random.default_rng([int(idx), 0x5EED])       # the dimensions added later: the draws above stay what they were
+    wkind = str(rng2.choice(["none", "pad", "frac", "sample"]))
+    teacher = bool(rng2.random() < 0.5)
+    partial = bool(rng2.random() < 0.5)
+    desc = dict(idx=idx, shape=shape, C=C, kpd=kpd, yuv=yuv, B=B, tiling=tiling, weights=wkind, teacher=teacher, partial=partial, **kw)
     cfg, p, coords, tgt, K = _setup(shape, C, kpd, yuv, B, 1000 + idx, **kw)
     dd = len(shape)
     if mode == 3 or kw.get("radial_as"):
@@ -79,7 +120,24 @@ def one_case(rng, idx):
         p["musX"] = (grid + rng.uniform(-0.05, 0.05, size=grid.shape)).astype(np.float32)
         cfg = o.OracleConfig(**{**cfg.__dict__, "mus_grid": grid})
         desc["centred"] = True
-    active = np.ones((B, K), bool)
+    active = np.ones((B, K), bool) if not partial else rng2.uniform(size=(B, K)) < 0.85
+    lw, fed = make_weights(wkind, shape, B, rng2, corner=min(2, B - 1))
+    lw_ref = None if ssim else lw                          # ssim_opt ignores the weights (smoe.py:929)
+    m0 = {k: np.zeros_like(v, dtype=np.float32) for k, v in p.items()}
+    v0 = {k: np.zeros_like(v, dtype=np.float32) for k, v in p.items()}
+    b1p, b2p, step0 = np.float32(cfg.beta1), np.float32(cfg.beta2), 0
+    if teacher:
+        ast = o.new_adam_state(p)
+        pt, at = {k: v.astype(np.float32) for k, v in p.items()}, active
+        for _ in range(WARMUP):
+            f = o.forward(pt, tgt, coords, at, cfg, lw_ref, np.float32, want_grads=True, fed=fed)
+            at = f["active_new"]
+            pt = o.adam_step(pt, f["grads"], ast, cfg, np.float32)
+        if all(np.isfinite(a).all() for d in (pt, ast["m"], ast["v"]) for a in d.values()):
+            p, active, m0, v0 = pt, at, ast["m"], ast["v"]
+            b1p, b2p, step0 = np.float32(ast["b1p"]), np.float32(ast["b2p"]), WARMUP
+        else:
+            desc["teacher"] = teacher = False              # the warm-up left the domain (a quantised diagonal on 0): fresh state
     try:
         eng = _engine(shape, C, K, use_yuv=yuv, **kw)
     except Exception as e:                                   # unsupported shape / combination: must say so
@@ -99,27 +157,44 @@ def one_case(rng, idx):
             eng.set_center_grid(gdev)
         act = torch.from_numpy(_mask_to_bits(active).view(np.int32)).cuda()
         T = _planar(tgt)
-        fw = eng.forward(T, dp, act, want_recon=True, update_active=False)
+        LW = None if lw is None else torch.from_numpy(lw).cuda()
+        try:
+            fw = eng.forward(T, dp, act, loss_w=LW, want_recon=True, update_active=False)
+        except Exception as e:
+            # a forced tiling that cannot hold the block once it carries weights is refused (never served by another kernel):
+            # such a case runs with the automatic choice
+            if not (tiling and LW is not None and "fits this block size" in str(e)):
+                raise
+            eng.set_tiling(0)
+            desc["tiling"] = 0
+            fw = eng.forward(T, dp, act, loss_w=LW, want_recon=True, update_active=False)
         recon = np.transpose(fw["recon"].cpu().numpy(), (0, 2, 1))
         if mode:
             q32, back, _ = o.quantize_graph_params(p, cfg, np.float32)
             cfg0 = o.OracleConfig(**{**cfg.__dict__, "quantization_mode": 0, "quantize_pis": False})
-            ref = o.forward(q32, tgt, coords, active, cfg0, None, np.float64, want_grads=True, q_override=recon)
+            ref = o.forward(q32, tgt, coords, active, cfg0, lw_ref, np.float64, want_grads=True, q_override=recon, fed=fed)
             ref["grads"] = o.route_quant_grads(ref["grads"], back, np.float64)
         else:
-            ref = o.forward(p, tgt, coords, active, cfg, None, np.float64, want_grads=True, q_override=recon)
+            ref = o.forward(p, tgt, coords, active, cfg, lw_ref, np.float64, want_grads=True, q_override=recon, fed=fed)
         frac = (np.clip(ref["y"], 0, 1) * 255 + 0.5) % 1.0
         tie_px = (frac < 3e-4) | (frac > 1 - 3e-4)
         lerr = np.abs(fw["loss"].cpu().numpy() - ref["loss"]).max()
         st = eng.new_adam_state(dp)
-        eng.fit(T, dp, st, act, 1)
+        for k in o.PARAM_NAMES:
+            st.m[k].copy_(torch.from_numpy(np.ascontiguousarray(m0[k], dtype=np.float32)))
+            st.v[k].copy_(torch.from_numpy(np.ascontiguousarray(v0[k], dtype=np.float32)))
+        st.c.beta1_power, st.c.beta2_power, st.c.step = float(b1p), float(b2p), step0
+        eng.fit(T, dp, st, act, 1, loss_w=LW, loss_w_is_sample=fed is not None)
         torch.cuda.synchronize()
+        desc["kernel"] = eng.last_fit_variant()
+        assert ("+lw" in desc["kernel"]) == (lw is not None), desc["kernel"]
         tie = (np.abs(ref["w"] - 0.5 / 256) < 1e-6).any(axis=(1, 2))
         edge = ((np.abs(ref["y"]) < 1e-6) | (np.abs(ref["y"] - 1) < 1e-6)).any(axis=(1, 2))
         # the fit kernel hoists lane-constant terms, the evaluation kernel does not: their y can differ in the last bits, so a
         # pixel whose y*255 sits on a rounding tie may quantise one level apart in the two kernels -- such blocks are skipped
         clean = ~(tie | edge | tie_px.any(axis=(1, 2)))
-        m = _to_host(st.m)
+        # the gradient out of the slots: m' = m + (g - m) (1 - beta1); m = 0 for the fresh state
+        m = {k: (v - 0.9 * m0[k].astype(np.float64)) for k, v in _to_host(st.m).items()}
         worst = ("", 0.0)
         if clean.any():
             for name in o.PARAM_NAMES:
@@ -134,7 +209,7 @@ def one_case(rng, idx):
         note = ""
         if not ok and worst[0] and not mode:
             # how far the SAME arithmetic in fp32 on the CPU is from fp64 on this case: a conditioning problem shows here too
-            r32 = o.forward(p, tgt, coords, active, cfg, None, np.float32, want_grads=True, q_override=recon)
+            r32 = o.forward(p, tgt, coords, active, cfg, lw_ref, np.float32, want_grads=True, q_override=recon, fed=fed)
             g64, g32 = ref["grads"][worst[0]][clean], r32["grads"][worst[0]][clean]
             dev = np.abs(m[worst[0]][clean] / 0.1 - g64)
             where = np.unravel_index(np.argmax(dev), dev.shape)

@@ -30,7 +30,7 @@ EXPORTS = (
     "smoe_shared_forward", "smoe_shared_accumulate", "smoe_shared_apply", "smoe_shared_grad_buffer",
     "smoe_shared_fit", "smoe_shared_update_kernel_list", "smoe_shared_set_loss_weights",
     "smoe_set_center_grid", "smoe_shared_set_center_grid", "smoe_set_total_blocks", "smoe_padded_kernels_full", "smoe_shared_discard", "smoe_set_sampling",
-    "smoe_render", "smoe_shared_render",
+    "smoe_render", "smoe_shared_render", "smoe_last_fit_variant",
 )
 
 
@@ -111,6 +111,8 @@ def load() -> C.CDLL:
                                 C.POINTER(C.c_int32), C.POINTER(C.c_int64), fp, i32, fp, vp]
     lib.smoe_fit_variant.argtypes = [vp, i32]
     lib.smoe_fit_variant.restype = C.c_char_p
+    lib.smoe_last_fit_variant.argtypes = [vp]
+    lib.smoe_last_fit_variant.restype = C.c_char_p
     lib.smoe_fit_occupancy.argtypes = [vp, i32]
     lib.smoe_set_tiling.argtypes = [vp, i32]
     lib.smoe_set_total_blocks.argtypes = [vp, C.c_int64]
@@ -134,7 +136,7 @@ def load() -> C.CDLL:
     lib.smoe_shared_set_center_grid.argtypes = [vp, fp]
     for name in EXPORTS:
         fn = getattr(lib, name)
-        if name not in ("smoe_fit_variant", "smoe_last_error"):
+        if name not in ("smoe_fit_variant", "smoe_last_fit_variant", "smoe_last_error"):
             fn.restype = C.c_int
     _lib = lib
     return lib

@@ -1527,7 +1527,7 @@ __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu
     const bool has_loss0 = a.loss0 != nullptr;
     const bool has_reg = (a.reg_pi != 0.0f) || (a.reg_u != 0.0f);
     const bool has_quant = (a.kc.qmode != 0) || (a.kc.qpis != 0);
-    float last_loss = 0.0f, last_sse = 0.0f;
+    float last_loss = no_pass_value(), last_sse = no_pass_value();     // (smoe_device.h)
     __syncthreads();
 
     // ---- fake-quantised graph: (re)build the block's quantised image from the raw parameters in s_par.  Runs once here
@@ -2029,14 +2029,14 @@ __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu
                 pick(ka->m, tensor)[off] = s_mv[2 * j];
                 pick(ka->v, tensor)[off] = s_mv[2 * j + 1];
             } else if (j == Lt::S_LOSS) {
-                if (ka->loss_out != nullptr && ka->n_iters > 0) ka->loss_out[b] = last_loss;
+                if (ka->loss_out != nullptr && made_a_pass(last_loss)) ka->loss_out[b] = last_loss;
                 if (ka->diverged != nullptr) ka->diverged[b] = (s_par[Lt::LP_FROZEN] != 0.0f) ? 1u : 0u;
                 uint32_t mask = 0u;
 #pragma unroll
                 for (int k = 0; k < K; ++k) mask |= (s_par[Lt::LP_ACT + k] != 0.0f) ? (1u << k) : 0u;
                 ka->active[b] = mask;
             } else if (j == Lt::S_SSE) {
-                if (ka->sse_out != nullptr && ka->n_iters > 0) ka->sse_out[b] = last_sse;
+                if (ka->sse_out != nullptr && made_a_pass(last_sse)) ka->sse_out[b] = last_sse;
             }
         }
     }

@@ -35,6 +35,7 @@ struct smoe_context {
     int lw_is_sample;    // smoe_set_sampling: the loss_w of smoe_fit is a pixel sub-sample
     int simds;           // SIMDs of the device (4 per CU; 1 024 on MI355X): the batch-size thresholds of the tiling rules scale with it
     std::string variant_name;   // what smoe_fit_variant last returned (the team names are composed)
+    std::string last_fit_name;  // what the last smoe_fit launched (smoe_last_fit_variant)
     // resident wavefronts per CU of the fit kernels asked about so far: (variant, kind 0 plain / 1 pair / 2 duo, loss weights) -> count
     std::vector<std::pair<std::tuple<const void*, int, int>, int>> occ_cache;
     smoe::KernelConsts kc;
@@ -641,6 +642,10 @@ const char* smoe_fit_variant(smoe_handle h, int32_t num_blocks) {
     return v ? v->name : "";
 }
 
+const char* smoe_last_fit_variant(smoe_handle h) {
+    return h ? h->last_fit_name.c_str() : "";
+}
+
 int smoe_fit_occupancy(smoe_handle h, int32_t num_blocks) {
     if (!h) return fail(SMOE_ERR_INVALID, "smoe_fit_occupancy: null handle");
     const smoe::Variant* v = find_variant(h, num_blocks, false);
@@ -745,6 +750,26 @@ int smoe_fit(smoe_handle h, int32_t num_blocks, const float* target, const float
     else if (h->kc.qmode) HIP_TRY(v->fit_quant(a, hoist, (hipStream_t)stream), "smoe_fit (quantised) launch");
     else if (h->kc.inverse_cov) HIP_TRY(v->fit_ic(a, hoist, (hipStream_t)stream), "smoe_fit (inverse covariance) launch");
     else HIP_TRY(v->fit(a, hoist, (hipStream_t)stream), "smoe_fit launch");
+    {
+        // a launch that came about: its name (smoe_last_fit_variant).  A failed one returned above and leaves the name of the
+        // last kernel that did run
+        std::string& nm = h->last_fit_name;
+        if (vduo || team > 0) {
+            nm = vduo ? vduo->name : v16->name;
+            const size_t g = nm.find(vduo ? "_g64" : "_g16");
+            if (g != std::string::npos) nm.resize(g);
+            if (vduo) nm += "_duo64w2";
+            else { nm += "_team16w"; nm += std::to_string(team); }
+        } else {
+            nm = v->name;
+            if (c.ssim_opt) nm += "+ssim";
+            else if (h->kc.qmode) nm += "+quant";
+            else if (h->kc.inverse_cov) nm += "+ic";
+            else if (a.pair) nm += "_pair";
+        }
+        if (loss_w != nullptr) nm += "+lw";         // (the SSIM loss ignores the weights, but its LDS layout makes room for them)
+        if (a.lw_is_sample) nm += "+sample";
+    }
     // TF multiplies the beta powers after every apply (fp32 running product)
     for (int i = 0; i < n_iters; ++i) {
         s->beta1_power *= c.beta1;

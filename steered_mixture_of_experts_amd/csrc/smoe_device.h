@@ -11,6 +11,19 @@
 
 namespace smoe {
 
+// What the fit kernels start a block's "loss / SSE of the last pass" from: a signalling-NaN pattern that no arithmetic
+// produces (results are quieted) and that only selects carry.  A block that is frozen when the launch starts makes no pass,
+// still holds the pattern at the write-back and leaves its loss_last / sse_last entries as the caller passed them: what a
+// caller reads there does not depend on how the iterations were split over launches.
+#define SMOE_NO_PASS_BITS 0x7fa0deadu
+#if defined(__FINITE_MATH_ONLY__) && __FINITE_MATH_ONLY__
+#error "SMOE_NO_PASS_BITS is a NaN pattern carried in a float: do not build these kernels with -ffinite-math-only / -ffast-math"
+#endif
+#if defined(__HIPCC__)
+__device__ __forceinline__ float no_pass_value() { return __uint_as_float(SMOE_NO_PASS_BITS); }
+__device__ __forceinline__ bool made_a_pass(float last) { return __float_as_uint(last) != SMOE_NO_PASS_BITS; }
+#endif
+
 // Block-independent constants of the forward / loss maths.
 struct KernelConsts {
     float tau;          // 0.5 / 2^p                       smoe.py:825

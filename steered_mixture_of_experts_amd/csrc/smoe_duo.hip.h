@@ -204,7 +204,7 @@ __global__ void __launch_bounds__(128) fit_duo_kernel(FitArgs a) {
     }
     const float loss0 = has_loss0 ? a.loss0[b] : 0.0f;
     float b1p = a.b1p, b2p = a.b2p;
-    float last_loss = 0.0f, last_sse = 0.0f;
+    float last_loss = no_pass_value(), last_sse = no_pass_value();     // (smoe_device.h)
     int cur = 0;
     __syncthreads();
 #pragma unroll
@@ -400,14 +400,14 @@ __global__ void __launch_bounds__(128) fit_duo_kernel(FitArgs a) {
             pick(a.m, tensor)[off] = mv[q];
             pick(a.v, tensor)[off] = vv[q];
         } else if (j == Lt::S_LOSS) {
-            if (a.loss_out != nullptr && a.n_iters > 0) a.loss_out[b] = last_loss;
+            if (a.loss_out != nullptr && made_a_pass(last_loss)) a.loss_out[b] = last_loss;
             if (a.diverged != nullptr) a.diverged[b] = (par[Lt::LP_FROZEN] != 0.0f) ? 1u : 0u;
             uint32_t mask = 0u;
 #pragma unroll
             for (int k = 0; k < K; ++k) mask |= (par[Lt::LP_ACT + k] != 0.0f) ? (1u << k) : 0u;
             a.active[b] = mask;
         } else if (j == Lt::S_SSE) {
-            if (a.sse_out != nullptr && a.n_iters > 0) a.sse_out[b] = last_sse;
+            if (a.sse_out != nullptr && made_a_pass(last_sse)) a.sse_out[b] = last_sse;
         }
     }
 }

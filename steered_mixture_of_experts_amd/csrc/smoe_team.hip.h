@@ -225,7 +225,7 @@ __global__ void __launch_bounds__(SMOE_TEAM_MAXW * 64) fit_team_kernel(FitArgs a
     __syncthreads();
 
     float b1p = a.b1p, b2p = a.b2p;
-    float last_loss = 0.0f, last_sse = 0.0f;
+    float last_loss = no_pass_value(), last_sse = no_pass_value();     // (smoe_device.h)
     int cur = 0;                                             // parameter buffer the graph of this iteration is built on
 
     for (int it = 0; it < a.n_iters; ++it) {
@@ -393,14 +393,14 @@ __global__ void __launch_bounds__(SMOE_TEAM_MAXW * 64) fit_team_kernel(FitArgs a
                 pick(a.m, tensor)[off] = s_mv[2 * j];
                 pick(a.v, tensor)[off] = s_mv[2 * j + 1];
             } else if (j == Lt::S_LOSS) {
-                if (a.loss_out != nullptr && a.n_iters > 0) a.loss_out[b] = last_loss;
+                if (a.loss_out != nullptr && made_a_pass(last_loss)) a.loss_out[b] = last_loss;
                 if (a.diverged != nullptr) a.diverged[b] = (par[Lt::LP_FROZEN] != 0.0f) ? 1u : 0u;
                 uint32_t mask = 0u;
 #pragma unroll
                 for (int k = 0; k < K; ++k) mask |= (par[Lt::LP_ACT + k] != 0.0f) ? (1u << k) : 0u;
                 a.active[b] = mask;
             } else if (j == Lt::S_SSE) {
-                if (a.sse_out != nullptr && a.n_iters > 0) a.sse_out[b] = last_sse;
+                if (a.sse_out != nullptr && made_a_pass(last_sse)) a.sse_out[b] = last_sse;
             }
         }
     }

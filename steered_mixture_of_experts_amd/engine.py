@@ -202,6 +202,11 @@ class BlockEngine:
     def fit_variant(self, B: int) -> str:
         return self.lib.smoe_fit_variant(self._h, B).decode()
 
+    def last_fit_variant(self) -> str:
+        """Name of the kernel the last ``fit`` launched, with its tiling / graph / loss-weight marks (include/smoe_hip.h:
+        smoe_last_fit_variant); "" before the first launch."""
+        return self.lib.smoe_last_fit_variant(self._h).decode()
+
     # -- the hot path ------------------------------------------------------------
     def forward(self, target, params, active, loss_w=None, want_recon=True, want_argmax=False,
                 want_gate=False, update_active=True):

@@ -456,8 +456,9 @@ class Smoe:
             return loss_val, mse_val, num_pi, 0
         if train:
             assert self.optimizer1 is not None, "no optimizer found, you have to specify one!"
-            loss = torch.empty((self.B,), dtype=torch.float32, device=eng.device)
-            sse = torch.empty((self.B,), dtype=torch.float32, device=eng.device)
+            # (zeros, not empty: smoe_fit leaves the entries of the blocks that were frozen before this pass untouched)
+            loss = torch.zeros((self.B,), dtype=torch.float32, device=eng.device)
+            sse = torch.zeros((self.B,), dtype=torch.float32, device=eng.device)
             eng.fit(self._target, self._params, self._state, self._active, 1,
                     loss_w=self._loss_w if sub_w is None else sub_w,
                     diverged=self._diverged, loss0=self._loss0, loss_out=loss, sse_out=sse,

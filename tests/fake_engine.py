@@ -167,6 +167,9 @@ class OracleEngine:
     def fit_variant(self, B):
         return "oracle"
 
+    def last_fit_variant(self):
+        return "oracle"
+
     def set_total_blocks(self, total_blocks):
         self.total_blocks = int(total_blocks)       # the oracle has one summation order: nothing to choose
 
