@@ -2453,248 +2453,204 @@ inline hipError_t allow_lds(const void* kern, size_t bytes) {
     return e;
 }
 
-template <int D, int C, int K, int G, int WAVES>
-hipError_t launch_fit(const FitArgs& a, int hoist, hipStream_t st) {
-    using T = Tile<D, C, K, G, WAVES>;
-    auto kern = fit_kernel<D, C, K, G, WAVES, 0>;
-    int hl = 0;
-    if (hoist >= 1) { kern = fit_kernel<D, C, K, G, WAVES, 1>; hl = 1; }
-    if (D == 3 && hoist >= 2) { kern = fit_kernel<D, C, K, G, WAVES, (D == 3 ? 2 : 1)>; hl = 2; }
-    int nb = T::NB;
-    if constexpr (G == 64 && WAVES == 2) {
-        if (a.pair) {                                  // one block on both wavefronts of the workgroup (see fit_kernel)
-            kern = fit_kernel<D, C, K, G, WAVES, 0, false, false, false, true>;
-            if (hl == 1) kern = fit_kernel<D, C, K, G, WAVES, 1, false, false, false, true>;
-            if (hl == 2) kern = fit_kernel<D, C, K, G, WAVES, (D == 3 ? 2 : 1), false, false, false, true>;
-            nb = 1;
-        }
-    }
-    const size_t shm = T::bytes(a.N, a.loss_w != nullptr, D - hl, false);
-    FitArgs aa = a;
-    size_t shm_all = shm;
-    aa.desc_off = 0;
-    if (T::wants_owner_post(a.N)) { aa.desc_off = (int)(shm / sizeof(float)); shm_all += sizeof(float) * (size_t)T::NB * T::DESC_STRIDE; }
-    hipError_t e = allow_lds(reinterpret_cast<const void*>(kern), shm_all);
+// The tail of every fit / evaluation launch (the team and duo launchers of smoe_team.hip.h / smoe_duo.hip.h included): let the
+// kernel have its dynamic LDS, tell it how much that is, launch.
+template <typename Args>
+hipError_t launch_with_lds(void (*kern)(Args), int grid, int threads, size_t lds, Args a, hipStream_t st) {
+    const hipError_t e = allow_lds(reinterpret_cast<const void*>(kern), lds);
     if (e != hipSuccess) return e;
-    const int grid = (a.B + nb - 1) / nb;
-    aa.lds_floats = (int)(shm_all / sizeof(float));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(T::THREADS), shm_all, st, aa);
+    a.lds_floats = (int)(lds / sizeof(float));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, a);
     return hipGetLastError();
 }
 
-template <int D, int C, int K, int G, int WAVES>
-hipError_t launch_fwd(const FwdArgs& a, hipStream_t st) {
-    using T = Tile<D, C, K, G, WAVES>;
-    const bool outs = (a.recon != nullptr) || (a.gate_w != nullptr) || (a.argmax != nullptr);
-    auto kern = outs ? forward_kernel<D, C, K, G, WAVES, false, false, false, 0, 2> : forward_kernel<D, C, K, G, WAVES, false, false, false, 0, 1>;
-    int hl = 0;
-    if (a.hoist >= 1) {
-        kern = outs ? forward_kernel<D, C, K, G, WAVES, false, false, false, 1, 2> : forward_kernel<D, C, K, G, WAVES, false, false, false, 1, 1>;
-        hl = 1;
-    }
-    if (D == 3 && a.hoist >= 2) {
-        kern = outs ? forward_kernel<D, C, K, G, WAVES, false, false, false, (D == 3 ? 2 : 1), 2>
-                    : forward_kernel<D, C, K, G, WAVES, false, false, false, (D == 3 ? 2 : 1), 1>;
-        hl = 2;
-    }
-    FwdArgs aa = a;
-    aa.regt = ((a.N + G - 1) / G <= T::FWD_PXR) ? 1 : 0;
-    const size_t shm = aa.regt ? sizeof(float) * (size_t)T::off_tgt(a.N, D - hl) : T::bytes(a.N, a.loss_w != nullptr, D - hl);
-    hipError_t e = allow_lds(reinterpret_cast<const void*>(kern), shm);
-    if (e != hipSuccess) return e;
-    const int grid = (a.B + T::NB - 1) / T::NB;
-    aa.lds_floats = (int)(shm / sizeof(float));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(T::THREADS), shm, st, aa);
-    return hipGetLastError();
-}
-
-// quantization_mode 2 / 3 launches
-template <int D, int C, int K, int G, int WAVES>
-hipError_t launch_fit_quant(const FitArgs& a, int hoist, hipStream_t st) {
-    using T = Tile<D, C, K, G, WAVES>;
-    const bool ic = a.kc.inverse_cov != 0;
-    auto kern = ic ? fit_kernel<D, C, K, G, WAVES, 0, false, true, true> : fit_kernel<D, C, K, G, WAVES, 0, false, true>;
-    int hl = 0;
-    if (hoist >= 1) { kern = ic ? fit_kernel<D, C, K, G, WAVES, 1, false, true, true> : fit_kernel<D, C, K, G, WAVES, 1, false, true>; hl = 1; }
-    if (D == 3 && hoist >= 2) {
-        kern = ic ? fit_kernel<D, C, K, G, WAVES, (D == 3 ? 2 : 1), false, true, true> : fit_kernel<D, C, K, G, WAVES, (D == 3 ? 2 : 1), false, true>;
-        hl = 2;
-    }
-    const size_t shm = T::bytes(a.N, a.loss_w != nullptr, D - hl, true);
-    FitArgs aa = a;
-    size_t shm_all = shm;
-    aa.desc_off = 0;
-    if (T::wants_owner_post(a.N)) { aa.desc_off = (int)(shm / sizeof(float)); shm_all += sizeof(float) * (size_t)T::NB * T::DESC_STRIDE; }
-    hipError_t e = allow_lds(reinterpret_cast<const void*>(kern), shm_all);
-    if (e != hipSuccess) return e;
-    const int grid = (a.B + T::NB - 1) / T::NB;
-    aa.lds_floats = (int)(shm_all / sizeof(float));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(T::THREADS), shm_all, st, aa);
-    return hipGetLastError();
-}
-
-template <int D, int C, int K, int G, int WAVES>
-hipError_t launch_fwd_quant(const FwdArgs& a, hipStream_t st) {
-    using T = Tile<D, C, K, G, WAVES>;
-    const bool ic = a.kc.inverse_cov != 0;
-    auto kern = ic ? forward_kernel<D, C, K, G, WAVES, false, true, true> : forward_kernel<D, C, K, G, WAVES, false, true>;
-    int hl = 0;
-    if (a.hoist >= 1) { kern = ic ? forward_kernel<D, C, K, G, WAVES, false, true, true, 1> : forward_kernel<D, C, K, G, WAVES, false, true, false, 1>; hl = 1; }
-    FwdArgs aa = a;
-    aa.regt = ((a.N + G - 1) / G <= T::FWD_PXR) ? 1 : 0;
-    const size_t shm = aa.regt ? sizeof(float) * (size_t)T::off_tgt(a.N, D - hl) : T::bytes(a.N, a.loss_w != nullptr, D - hl);
-    hipError_t e = allow_lds(reinterpret_cast<const void*>(kern), shm);
-    if (e != hipSuccess) return e;
-    const int grid = (a.B + T::NB - 1) / T::NB;
-    aa.lds_floats = (int)(shm / sizeof(float));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(T::THREADS), shm, st, aa);
-    return hipGetLastError();
-}
-
-// train_inverse_cov launches for the margin loss without mode-2/3 quantisation (the SSIM and QUANT launchers pick
-// their own IC instantiations)
-template <int D, int C, int K, int G, int WAVES>
-hipError_t launch_fit_ic(const FitArgs& a, int hoist, hipStream_t st) {
-    using T = Tile<D, C, K, G, WAVES>;
-    auto kern = fit_kernel<D, C, K, G, WAVES, 0, false, false, true>;
-    int hl = 0;
-    if (hoist >= 1) { kern = fit_kernel<D, C, K, G, WAVES, 1, false, false, true>; hl = 1; }
-    if (D == 3 && hoist >= 2) { kern = fit_kernel<D, C, K, G, WAVES, (D == 3 ? 2 : 1), false, false, true>; hl = 2; }
-    const size_t shm = T::bytes(a.N, a.loss_w != nullptr, D - hl, false);
-    FitArgs aa = a;
-    size_t shm_all = shm;
-    aa.desc_off = 0;
-    if (T::wants_owner_post(a.N)) { aa.desc_off = (int)(shm / sizeof(float)); shm_all += sizeof(float) * (size_t)T::NB * T::DESC_STRIDE; }
-    hipError_t e = allow_lds(reinterpret_cast<const void*>(kern), shm_all);
-    if (e != hipSuccess) return e;
-    const int grid = (a.B + T::NB - 1) / T::NB;
-    aa.lds_floats = (int)(shm_all / sizeof(float));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(T::THREADS), shm_all, st, aa);
-    return hipGetLastError();
-}
-
-template <int D, int C, int K, int G, int WAVES>
-hipError_t launch_fwd_ic(const FwdArgs& a, hipStream_t st) {
-    using T = Tile<D, C, K, G, WAVES>;
-    auto kern = forward_kernel<D, C, K, G, WAVES, false, false, true>;
-    int hl = 0;
-    if (a.hoist >= 1) { kern = forward_kernel<D, C, K, G, WAVES, false, false, true, 1>; hl = 1; }
-    if (D == 3 && a.hoist >= 2) { kern = forward_kernel<D, C, K, G, WAVES, false, false, true, (D == 3 ? 2 : 1)>; hl = 2; }
-    FwdArgs aa = a;
-    aa.regt = ((a.N + G - 1) / G <= T::FWD_PXR) ? 1 : 0;
-    const size_t shm = aa.regt ? sizeof(float) * (size_t)T::off_tgt(a.N, D - hl) : T::bytes(a.N, a.loss_w != nullptr, D - hl);
-    hipError_t e = allow_lds(reinterpret_cast<const void*>(kern), shm);
-    if (e != hipSuccess) return e;
-    const int grid = (a.B + T::NB - 1) / T::NB;
-    aa.lds_floats = (int)(shm / sizeof(float));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(T::THREADS), shm, st, aa);
-    return hipGetLastError();
-}
-
-// ssim_opt launches: 2-d blocks on the 16- and 64-lane tilings, 3-d blocks on the one-block-per-wavefront tiling
-template <int D, int C, int K, int G, int WAVES>
-hipError_t launch_fit_ssim(const FitArgs& a, int hoist, hipStream_t st) {
-    if constexpr (D == 2 || (D == 3 && G == 64)) {
-        using T = Tile<D, C, K, G, WAVES>;
-        if (G == 16 && (a.bh != 16 || a.bw != 16 || hoist < 1)) return hipErrorNotSupported;   // register path: 16x16 only
-        const bool ic = a.kc.inverse_cov != 0;
-        const bool q = a.kc.qmode >= 2;             // all variables fake-quantised: the QUANT instantiation of the SSIM kernel
-        constexpr int H0 = (G == 16) ? 1 : 0;
-        auto kern = q ? (ic ? fit_kernel<D, C, K, G, WAVES, H0, true, true, true> : fit_kernel<D, C, K, G, WAVES, H0, true, true>)
-                      : (ic ? fit_kernel<D, C, K, G, WAVES, H0, true, false, true> : fit_kernel<D, C, K, G, WAVES, H0, true>);
-        int hl = H0;
-        if (hoist >= 1) {
-            kern = q ? (ic ? fit_kernel<D, C, K, G, WAVES, 1, true, true, true> : fit_kernel<D, C, K, G, WAVES, 1, true, true>)
-                     : (ic ? fit_kernel<D, C, K, G, WAVES, 1, true, false, true> : fit_kernel<D, C, K, G, WAVES, 1, true>);
-            hl = 1;
-        }
-        const size_t shm = T::bytes_ssim(a.N, a.loss_w != nullptr, D - hl, a.bh, a.bw, q, (D == 3) ? a.bt : 0);
-    FitArgs aa = a;
-    size_t shm_all = shm;
-    aa.desc_off = 0;
-    if (T::wants_owner_post(a.N)) { aa.desc_off = (int)(shm / sizeof(float)); shm_all += sizeof(float) * (size_t)T::NB * T::DESC_STRIDE; }
-        hipError_t e = allow_lds(reinterpret_cast<const void*>(kern), shm_all);
-        if (e != hipSuccess) return e;
-        const int grid = (a.B + T::NB - 1) / T::NB;
-        aa.lds_floats = (int)(shm_all / sizeof(float));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(T::THREADS), shm_all, st, aa);
-        return hipGetLastError();
-    } else {
-        return hipErrorNotSupported;
-    }
-}
-
-template <int D, int C, int K, int G, int WAVES>
-hipError_t launch_fwd_ssim(const FwdArgs& a, hipStream_t st) {
-    if constexpr (D == 2 || (D == 3 && G == 64)) {
-        using T = Tile<D, C, K, G, WAVES>;
-        if (G == 16 && (a.bh != 16 || a.bw != 16)) return hipErrorNotSupported;
-        const size_t shm = T::bytes_ssim(a.N, a.loss_w != nullptr, D, a.bh, a.bw, false, (D == 3) ? a.bt : 0);
-        const bool q = a.kc.qmode >= 2;
-        auto kern = q ? (a.kc.inverse_cov ? forward_kernel<D, C, K, G, WAVES, true, true, true> : forward_kernel<D, C, K, G, WAVES, true, true>)
-                      : (a.kc.inverse_cov ? forward_kernel<D, C, K, G, WAVES, true, false, true> : forward_kernel<D, C, K, G, WAVES, true>);
-        hipError_t e = allow_lds(reinterpret_cast<const void*>(kern), shm);
-        if (e != hipSuccess) return e;
-        const int grid = (a.B + T::NB - 1) / T::NB;
-        FwdArgs aa = a;
-        aa.regt = 0;
-        aa.lds_floats = (int)(shm / sizeof(float));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(T::THREADS), shm, st, aa);
-        return hipGetLastError();
-    } else {
-        return hipErrorNotSupported;
-    }
-}
-
-template <int D, int C, int K, int G, int WAVES>
-size_t lds_bytes(int N, bool has_lw, bool hq) { return Tile<D, C, K, G, WAVES>::bytes(N, has_lw, D, hq); }
-
-template <int D, int C, int K, int G, int WAVES>
-size_t lds_bytes_ssim(int N, bool has_lw, int bh, int bw, int bt, bool hq) {
-    if (!(D == 2 || (D == 3 && G == 64)) || (G == 16 && (bh != 16 || bw != 16))) return (size_t)-1;
-    return Tile<D, C, K, G, WAVES>::bytes_ssim(N, has_lw, D, bh, bw, hq, (D == 3) ? bt : 0);
-}
-
-template <int D, int C, int K, int G, int WAVES>
-int fit_occupancy(int N, bool has_lw, int hoist, bool pair) {
-    using T = Tile<D, C, K, G, WAVES>;
+// ... and of every occupancy query: workgroups of that launch a CU holds at once, -1 = unknown (no device)
+template <typename Args>
+int resident_workgroups(void (*kern)(Args), int threads, size_t lds) {
     int nb = 0;
-    auto kern = fit_kernel<D, C, K, G, WAVES, 0>;
-    int hl = 0;
-    if (hoist >= 1) { kern = fit_kernel<D, C, K, G, WAVES, 1>; hl = 1; }
-    if (D == 3 && hoist >= 2) { kern = fit_kernel<D, C, K, G, WAVES, (D == 3 ? 2 : 1)>; hl = 2; }
-    if constexpr (G == 64 && WAVES == 2) {
-        if (pair) {
-            kern = fit_kernel<D, C, K, G, WAVES, 0, false, false, false, true>;
-            if (hl == 1) kern = fit_kernel<D, C, K, G, WAVES, 1, false, false, false, true>;
-            if (hl == 2) kern = fit_kernel<D, C, K, G, WAVES, (D == 3 ? 2 : 1), false, false, false, true>;
-        }
-    }
-    size_t shm = T::bytes(N, has_lw, D - hl);
-    if (T::wants_owner_post(N)) shm += sizeof(float) * (size_t)T::NB * T::DESC_STRIDE;
-    if (allow_lds(reinterpret_cast<const void*>(kern), shm) != hipSuccess) return -1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, T::THREADS, shm) != hipSuccess) return -1;
-    return nb * WAVES;       // resident wavefronts per CU
+    if (allow_lds(reinterpret_cast<const void*>(kern), lds) != hipSuccess) return -1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, threads, lds) != hipSuccess) return -1;
+    return nb;
 }
 
+// What a resolver makes of (graph, block size, hoisting level of the tiling): the one instantiation that runs it and the
+// shape of its launch.  kern == null: this variant has no kernel for the graph.
+template <typename Args>
+struct Launch {
+    void (*kern)(Args) = nullptr;
+    int hl = 0;              // hoisting level of the instantiation (<= the tiling's)
+    int threads = 0, nb = 1; // per workgroup: threads, blocks
+    size_t lds = 0;          // dynamic LDS, the owner-post descriptors included
+    int desc_off = 0;        // fit: FitArgs::desc_off
+    int regt = 0;            // evaluation: FwdArgs::regt
+};
+
+// the instantiations of one graph for the hoisting levels HMIN .. HMAX; picks min(hl, HMAX)
+template <int D, int C, int K, int G, int WAVES, bool SSIM, bool QUANT, bool IC, bool PAIR, int HMIN, int HMAX>
+auto fit_kernel_at(int hl) -> void (*)(FitArgs) {
+    if constexpr (HMAX > HMIN) {
+        if (hl < HMAX) return fit_kernel_at<D, C, K, G, WAVES, SSIM, QUANT, IC, PAIR, HMIN, HMAX - 1>(hl);
+    }
+    return fit_kernel<D, C, K, G, WAVES, HMAX, SSIM, QUANT, IC, PAIR>;
+}
+
+template <int D, int C, int K, int G, int WAVES, bool SSIM, bool QUANT, bool IC, int OM, int HMAX>
+auto forward_kernel_at(int hl) -> void (*)(FwdArgs) {
+    if constexpr (HMAX > 0) {
+        if (hl < HMAX) return forward_kernel_at<D, C, K, G, WAVES, SSIM, QUANT, IC, OM, HMAX - 1>(hl);
+    }
+    return forward_kernel<D, C, K, G, WAVES, SSIM, QUANT, IC, HMAX, OM>;
+}
+
+// Which fit_kernel runs a graph on this tiling.  FULL = the triple is built with the SSIM and mode-2/3 kernels
+// (smoe_variants.def); every other instantiation exists for every variant.  The levels differ per graph, and a level
+// fixes the order of a pixel's fused multiply-adds, so they are part of what the library computes:
+//   plain / ic / quant (x ic)  HL 0, 1 and, 3-d blocks, 2; LDS of Tile::bytes with D - HL coordinate rows, quant with the image
+//   pair                       the plain graph on the 64-lane two-wavefront tiling only (elsewhere: the plain kernel); one
+//                              block per workgroup, the descriptor region still sized for Tile::NB
+//   ssim                       2-d blocks, 3-d blocks on 64 lanes; HL 0 or 1, never 2; 16 lanes: HL 1 only, and only 16x16
+//                              blocks whose tiling hoists; LDS of Tile::bytes_ssim; QUANT and IC instantiations by the flags
+template <int D, int C, int K, int G, int WAVES, bool FULL>
+Launch<FitArgs> resolve_fit(Graph g, int N, bool has_lw, int hoist, int bh, int bw, int bt) {
+    using T = Tile<D, C, K, G, WAVES>;
+    constexpr int HMAX = (D == 3) ? 2 : 1;
+    Launch<FitArgs> r;
+    r.threads = T::THREADS;
+    r.nb = T::NB;
+    size_t shm = 0;
+    if (g.ssim) {
+        if constexpr (FULL && (D == 2 || (D == 3 && G == 64))) {
+            if (G == 16 && (bh != 16 || bw != 16 || hoist < 1)) return r;       // register path: 16x16 only
+            constexpr int H0 = (G == 16) ? 1 : 0;
+            r.hl = (hoist >= 1) ? 1 : H0;
+            r.kern = g.quant ? (g.ic ? fit_kernel_at<D, C, K, G, WAVES, true, true, true, false, H0, 1>(r.hl)
+                                     : fit_kernel_at<D, C, K, G, WAVES, true, true, false, false, H0, 1>(r.hl))
+                             : (g.ic ? fit_kernel_at<D, C, K, G, WAVES, true, false, true, false, H0, 1>(r.hl)
+                                     : fit_kernel_at<D, C, K, G, WAVES, true, false, false, false, H0, 1>(r.hl));
+            shm = T::bytes_ssim(N, has_lw, D - r.hl, bh, bw, g.quant, (D == 3) ? bt : 0);
+        } else {
+            return r;
+        }
+    } else {
+        r.hl = (hoist >= HMAX) ? HMAX : ((hoist >= 1) ? 1 : 0);
+        if (g.quant) {
+            if constexpr (FULL) {
+                r.kern = g.ic ? fit_kernel_at<D, C, K, G, WAVES, false, true, true, false, 0, HMAX>(r.hl)
+                              : fit_kernel_at<D, C, K, G, WAVES, false, true, false, false, 0, HMAX>(r.hl);
+            } else {
+                return r;
+            }
+        } else if (g.ic) {
+            r.kern = fit_kernel_at<D, C, K, G, WAVES, false, false, true, false, 0, HMAX>(r.hl);
+        } else {
+            r.kern = fit_kernel_at<D, C, K, G, WAVES, false, false, false, false, 0, HMAX>(r.hl);
+            if constexpr (G == 64 && WAVES == 2) {
+                if (g.pair) {                              // one block on both wavefronts of the workgroup (see fit_kernel)
+                    r.kern = fit_kernel_at<D, C, K, G, WAVES, false, false, false, true, 0, HMAX>(r.hl);
+                    r.nb = 1;
+                }
+            }
+        }
+        shm = T::bytes(N, has_lw, D - r.hl, g.quant);
+    }
+    if (T::wants_owner_post(N)) {          // the owner-side gradient descriptors follow the planes
+        r.desc_off = (int)(shm / sizeof(float));
+        shm += sizeof(float) * (size_t)T::NB * T::DESC_STRIDE;
+    }
+    r.lds = shm;
+    return r;
+}
+
+// Which forward_kernel evaluates a graph on this tiling:
+//   plain  HL 0, 1 and, 3-d blocks, 2; OM 2 with outputs (recon / gate_w / argmax), OM 1 without
+//   ic     the same levels, no OM
+//   quant  (x ic) HL 0 or 1 only: a 3-d launch whose tiling hoists two axes runs the HL 1 kernel and is sized for it
+//   ssim   (x quant x ic) where fit has it; HL 0, targets staged (regt = 0), LDS of Tile::bytes_ssim with all D coordinate
+//          rows and without the quantised image
+// regt: the block's pixels fit the lanes' registers, the launch stages no target planes and needs LDS up to them only.
+template <int D, int C, int K, int G, int WAVES, bool FULL>
+Launch<FwdArgs> resolve_fwd(Graph g, int N, bool has_lw, int hoist, int bh, int bw, int bt) {
+    using T = Tile<D, C, K, G, WAVES>;
+    constexpr int HMAX = (D == 3) ? 2 : 1;
+    Launch<FwdArgs> r;
+    r.threads = T::THREADS;
+    r.nb = T::NB;
+    if (g.ssim) {
+        if constexpr (FULL && (D == 2 || (D == 3 && G == 64))) {
+            if (G == 16 && (bh != 16 || bw != 16)) return r;
+            r.kern = g.quant ? (g.ic ? forward_kernel<D, C, K, G, WAVES, true, true, true> : forward_kernel<D, C, K, G, WAVES, true, true>)
+                             : (g.ic ? forward_kernel<D, C, K, G, WAVES, true, false, true> : forward_kernel<D, C, K, G, WAVES, true>);
+            r.lds = T::bytes_ssim(N, has_lw, D, bh, bw, false, (D == 3) ? bt : 0);
+        }
+        return r;
+    }
+    r.hl = (hoist >= HMAX) ? HMAX : ((hoist >= 1) ? 1 : 0);
+    if (g.quant) {
+        if constexpr (FULL) {
+            if (r.hl > 1) r.hl = 1;
+            r.kern = g.ic ? forward_kernel_at<D, C, K, G, WAVES, false, true, true, 0, 1>(r.hl)
+                          : forward_kernel_at<D, C, K, G, WAVES, false, true, false, 0, 1>(r.hl);
+        } else {
+            return r;
+        }
+    } else if (g.ic) {
+        r.kern = forward_kernel_at<D, C, K, G, WAVES, false, false, true, 0, HMAX>(r.hl);
+    } else {
+        r.kern = g.outs ? forward_kernel_at<D, C, K, G, WAVES, false, false, false, 2, HMAX>(r.hl)
+                        : forward_kernel_at<D, C, K, G, WAVES, false, false, false, 1, HMAX>(r.hl);
+    }
+    r.regt = ((N + G - 1) / G <= T::FWD_PXR) ? 1 : 0;
+    r.lds = r.regt ? sizeof(float) * (size_t)T::off_tgt(N, D - r.hl) : T::bytes(N, has_lw, D - r.hl);
+    return r;
+}
+
+template <int D, int C, int K, int G, int WAVES, bool FULL>
+hipError_t launch_fit(const FitArgs& a, Graph g, int hoist, hipStream_t st) {
+    const Launch<FitArgs> r = resolve_fit<D, C, K, G, WAVES, FULL>(g, a.N, a.loss_w != nullptr, hoist, a.bh, a.bw, a.bt);
+    if (!r.kern) return hipErrorNotSupported;
+    FitArgs aa = a;
+    aa.desc_off = r.desc_off;
+    return launch_with_lds(r.kern, (a.B + r.nb - 1) / r.nb, r.threads, r.lds, aa, st);
+}
+
+template <int D, int C, int K, int G, int WAVES, bool FULL>
+hipError_t launch_fwd(const FwdArgs& a, Graph g, hipStream_t st) {
+    const Launch<FwdArgs> r = resolve_fwd<D, C, K, G, WAVES, FULL>(g, a.N, a.loss_w != nullptr, a.hoist, a.bh, a.bw, a.bt);
+    if (!r.kern) return hipErrorNotSupported;
+    FwdArgs aa = a;
+    aa.regt = r.regt;
+    return launch_with_lds(r.kern, (a.B + r.nb - 1) / r.nb, r.threads, r.lds, aa, st);
+}
+
+// LDS a graph needs on this tiling at hoisting level 0 (the variant choice of smoe_capi.hip: the most any level needs);
+// (size_t)-1: the variant does not run the graph
+template <int D, int C, int K, int G, int WAVES, bool FULL>
+size_t lds_bytes(Graph g, int N, bool has_lw, int bh, int bw, int bt) {
+    if (!g.ssim) return Tile<D, C, K, G, WAVES>::bytes(N, has_lw, D, g.quant);
+    if (!FULL || !(D == 2 || (D == 3 && G == 64)) || (G == 16 && (bh != 16 || bw != 16))) return (size_t)-1;
+    return Tile<D, C, K, G, WAVES>::bytes_ssim(N, has_lw, D, bh, bw, g.quant, (D == 3) ? bt : 0);
+}
+
+// Resident wavefronts per CU of the plain (or pair) kernel of the tiling, whatever graph the handle runs (smoe_capi.hip says
+// what the answer is used for), sized without the quantised image.
+template <int D, int C, int K, int G, int WAVES, bool FULL>
+int fit_occupancy(int N, bool has_lw, int hoist, bool pair) {
+    Graph g = {};
+    g.pair = pair;
+    const Launch<FitArgs> r = resolve_fit<D, C, K, G, WAVES, FULL>(g, N, has_lw, hoist, 0, 0, 0);
+    const int nb = resident_workgroups(r.kern, r.threads, r.lds);
+    return (nb < 0) ? -1 : nb * WAVES;
+}
+
+// FULL = 0: the reduced instantiation for the (dim, channels, kernels) triples outside the BASELINE shapes and for the
+// 32-lane tiling: the margin loss with and without train_inverse_cov (quantize_pis included: it lives in the default
+// kernels); ssim_opt and quantization_mode 2 / 3 are refused (smoe_capi.hip) -- each costs a further set of kernels.
 #define SMOE_STR_(x) #x
 #define SMOE_STR(x) SMOE_STR_(x)
-#define SMOE_VARIANT(D, C, K, G, W) \
-    { D, C, K, G, W, "fit_d" SMOE_STR(D) "c" SMOE_STR(C) "k" SMOE_STR(K) "_g" SMOE_STR(G) "w" SMOE_STR(W), &launch_fit<D, C, K, G, W>, &launch_fwd<D, C, K, G, W>, &lds_bytes<D, C, K, G, W>, &fit_occupancy<D, C, K, G, W>, \
-      &launch_fit_ssim<D, C, K, G, W>, &launch_fwd_ssim<D, C, K, G, W>, &lds_bytes_ssim<D, C, K, G, W>, \
-      &launch_readmit_quant<D, C, K, G, W>, &launch_fit_quant<D, C, K, G, W>, &launch_fwd_quant<D, C, K, G, W>, \
-      &launch_fit_ic<D, C, K, G, W>, &launch_fwd_ic<D, C, K, G, W>, \
-      team_fit_ptr<D, C, K, G, W>(), team_lds_ptr<D, C, K, G, W>(), team_occ_ptr<D, C, K, G, W>(), \
-      duo_fit_ptr<D, C, K, G>(), duo_lds_ptr<D, C, K, G>(), duo_occ_ptr<D, C, K, G>(), \
-      &launch_render<D, C, K, (SMOE_FULL != 0)> }
-
-// Reduced instantiation for the (dim, channels, kernels) triples outside the BASELINE shapes: the margin loss with and
-// without train_inverse_cov (quantize_pis included: it lives in the default kernels); ssim_opt and quantization_mode
-// 2 / 3 are refused for these triples (smoe_capi.hip) -- each costs a further set of kernels per triple.
-#define SMOE_VARIANT_BASIC(D, C, K, G, W) \
-    { D, C, K, G, W, "fit_d" SMOE_STR(D) "c" SMOE_STR(C) "k" SMOE_STR(K) "_g" SMOE_STR(G) "w" SMOE_STR(W), &launch_fit<D, C, K, G, W>, &launch_fwd<D, C, K, G, W>, &lds_bytes<D, C, K, G, W>, &fit_occupancy<D, C, K, G, W>, \
-      nullptr, nullptr, nullptr, &launch_readmit_quant<D, C, K, G, W>, nullptr, nullptr, \
-      &launch_fit_ic<D, C, K, G, W>, &launch_fwd_ic<D, C, K, G, W>, \
+#define SMOE_VARIANT(D, C, K, G, W, FULL) \
+    { D, C, K, G, W, "fit_d" SMOE_STR(D) "c" SMOE_STR(C) "k" SMOE_STR(K) "_g" SMOE_STR(G) "w" SMOE_STR(W), (FULL) != 0, \
+      &launch_fit<D, C, K, G, W, (FULL) != 0>, &launch_fwd<D, C, K, G, W, (FULL) != 0>, &lds_bytes<D, C, K, G, W, (FULL) != 0>, \
+      &fit_occupancy<D, C, K, G, W, (FULL) != 0>, &launch_readmit_quant<D, C, K, G, W>, \
       team_fit_ptr<D, C, K, G, W>(), team_lds_ptr<D, C, K, G, W>(), team_occ_ptr<D, C, K, G, W>(), \
       duo_fit_ptr<D, C, K, G>(), duo_lds_ptr<D, C, K, G>(), duo_occ_ptr<D, C, K, G>(), \
       &launch_render<D, C, K, (SMOE_FULL != 0)> }

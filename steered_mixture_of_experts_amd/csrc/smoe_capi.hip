@@ -26,8 +26,6 @@ struct smoe_context {
     int force_g;
     const float* mus_grid;   // use_diff_center: kernel-grid centres [B,K,D] of the blocks the calls pass (smoe_set_center_grid), or null
     mutable int big_g;   // lanes per block for blocks of more than 512 pixels (big_block_lanes; -1: not asked yet)
-    int pair_occ;        // wavefronts per CU the 64-lane fit kernel reaches (-1: not asked yet)
-    mutable int duo_occ[2];   // wavefronts per CU of the duo kernel without / with loss weights (-2: not asked yet, -1: unknown)
     int force_pair;      // 0: by batch size, 1: one block per 2-wavefront workgroup (smoe_set_tiling 128), -1: never
     long long total_blocks;   // smoe_set_total_blocks: block count of the whole job the calls are shards of (0: each call's own)
     int force_team;      // 0: by batch size, 2 / 4 / 8: team tiling with that many wavefronts per workgroup, -1: never
@@ -36,8 +34,8 @@ struct smoe_context {
     int simds;           // SIMDs of the device (4 per CU; 1 024 on MI355X): the batch-size thresholds of the tiling rules scale with it
     std::string variant_name;   // what smoe_fit_variant last returned (the team names are composed)
     std::string last_fit_name;  // what the last smoe_fit launched (smoe_last_fit_variant)
-    // resident wavefronts per CU of the fit kernels asked about so far: (variant, kind 0 plain / 1 pair / 2 duo, loss weights) -> count
-    std::vector<std::pair<std::tuple<const void*, int, int>, int>> occ_cache;
+    // resident wavefronts per CU of the fit kernels asked about so far: (variant, TilingKind, loss weights) -> count (-1: unknown)
+    mutable std::vector<std::pair<std::tuple<const void*, int, int>, int>> occ_cache;
     smoe::KernelConsts kc;
     std::vector<float> h_coords;
 };
@@ -124,6 +122,16 @@ void ssim_axis_table(int b, float* out) {
         }
 }
 
+// the tap tables of a block / batch shape on the device: Tr [bh][11], Tc [bw][11], 3-d shapes (bt > 0): Tt [bt][11]
+hipError_t upload_ssim_tables(float** d_tabs, int bh, int bw, int bt) {
+    std::vector<float> tabs((size_t)11 * (bh + bw + bt));
+    ssim_axis_table(bh, tabs.data());
+    ssim_axis_table(bw, tabs.data() + (size_t)11 * bh);
+    if (bt) ssim_axis_table(bt, tabs.data() + (size_t)11 * (bh + bw));
+    const hipError_t e = dev_malloc(d_tabs, sizeof(float) * tabs.size());
+    return (e != hipSuccess) ? e : dev_upload(*d_tabs, tabs.data(), sizeof(float) * tabs.size());
+}
+
 // fake-quantised variables (smoe.py:474-538): nudged constants of the fixed ranges, TF Nudge() in fp32
 void fill_quant_consts(smoe::KernelConsts& kc, int mode, int quantize_pis, int train_musx, const int32_t* bits,
                        const float* lb, const float* ub) {
@@ -159,6 +167,38 @@ int check_quant_config(int mode, int quantize_pis, const int32_t* bits, const fl
     return SMOE_OK;
 }
 
+// Block-independent constants of a block handle (pixels = N of a block) or a shared-kernel handle (pixels = Nb of a batch:
+// the loss and SSIM means are per batch); the two config structs name these fields alike.
+template <typename Config>
+void fill_kernel_consts(smoe::KernelConsts& kc, const Config& cfg, long pixels) {
+    const double two_p = std::ldexp(1.0, cfg.precision);
+    kc.tau = (float)(0.5 * 1.0 / two_p);                 // smoe.py:825
+    kc.epsm = (float)((double)cfg.margin * 1.0 / two_p); // smoe.py:931
+    const float levels = (float)(two_p - 1.0);
+    kc.scale = 1.0f / levels;                            // TF Nudge(): (max-min)/(quant_max-quant_min)
+    kc.inv_scale = 1.0f / kc.scale;
+    kc.nudged_max = fminf(1.0f, levels * kc.scale);      // combined clip_by_value(0,1) + nudged range
+    const int C = cfg.channels;
+    for (int c = 0; c < SMOE_MAX_CHANNELS; ++c) kc.cw[c] = kc.sw[c] = 0.0f;
+    for (int c = 0; c < C; ++c) {
+        const double yuv = (c == 0) ? 6.0 / 8.0 : 1.0 / 8.0;
+        if (cfg.use_yuv) kc.cw[c] = (float)(yuv / (double)pixels);                               // smoe.py:934
+        else kc.cw[c] = (float)(1.0 / ((double)pixels * C));                                     // smoe.py:937
+        const double w = cfg.use_yuv ? yuv : 1.0 / (double)C;     // smoe.py:1006-1009, mean over the window positions
+        kc.sw[c] = (float)(w / (double)pixels);
+    }
+    kc.n_dis = (float)std::sqrt(std::pow(2.0 * M_PI, (double)cfg.dim));                          // smoe.py:812
+    kc.inv_n_dis = 1.0f / kc.n_dis;
+    kc.use_det = cfg.use_determinant ? 1 : 0;
+    kc.train_gammas = cfg.train_gammas ? 1 : 0;
+    kc.only_y_gamma = (cfg.only_y_gamma && cfg.use_yuv && cfg.train_gammas) ? 1 : 0;   // smoe.py:725
+    fill_quant_consts(kc, cfg.quantization_mode, cfg.quantize_pis, cfg.train_musx, cfg.bit_depths, cfg.lower_bounds, cfg.upper_bounds);
+    kc.inverse_cov = cfg.train_inverse_cov ? 1 : 0;
+    kc.radial = cfg.radial_as ? 1 : 0;
+    kc.kcount_norm = cfg.kernel_count_as_norm_l1 ? 1 : 0;
+    kc.pis_l1_raw = cfg.pis_l1;
+}
+
 // Lanes walk the block with stride G: when G is a multiple of the last axis (of the last two axes), a lane's last (two)
 // coordinate(s) never change and the kernels hoist every term in them out of the pixel loop (fit_kernel<..., HL>).
 int hoist_level(const smoe_context* h, const smoe::Variant* v) {
@@ -171,9 +211,35 @@ int hoist_level(const smoe_context* h, const smoe::Variant* v) {
 
 // What a launch needs from a variant (the basic instantiations of smoe_variants.def lack the SSIM / mode-2,3 kernels).
 bool variant_serves(const smoe::Variant& v, const smoe_context* h) {
-    if (h->cfg.ssim_opt) return v.fit_ssim != nullptr;
-    if (h->kc.qmode) return v.fit_quant != nullptr;
-    return true;
+    return (h->cfg.ssim_opt || h->kc.qmode) ? v.full : true;
+}
+
+smoe::Graph graph_of(const smoe_context* h) {
+    smoe::Graph g = {};
+    g.ssim = h->cfg.ssim_opt != 0;
+    g.quant = h->kc.qmode != 0;
+    g.ic = h->kc.inverse_cov != 0;
+    return g;
+}
+
+size_t variant_lds_bytes(const smoe::Variant& v, const smoe_context* h, bool has_lw) {
+    return v.lds_bytes(graph_of(h), h->N, has_lw, h->cfg.block_shape[0], h->cfg.block_shape[1], h->cfg.block_shape[2]);
+}
+
+// How smoe_fit lays the blocks of a launch on wavefronts
+enum TilingKind { TILE_PLAIN = 0, TILE_PAIR = 1, TILE_DUO = 2, TILE_TEAM = 3 };
+
+// Resident wavefronts per CU of the plain / pair / duo fit kernel of a variant (-1: unknown, no device), asked of the
+// device once per handle (an occupancy query per launch would cost the short launches of a small batch microseconds).
+// The SSIM / quantised / inverse-covariance graphs are answered with the plain kernel of their tiling.
+int fit_waves_per_cu(const smoe_context* h, const smoe::Variant* v, int kind, bool has_lw) {
+    const auto key = std::make_tuple((const void*)v, kind, (int)has_lw);
+    for (const auto& e : h->occ_cache)
+        if (e.first == key) return e.second;
+    const int hl = hoist_level(h, v);
+    const int occ = (kind == TILE_DUO) ? v->duo_waves_per_cu(h->N, has_lw, hl) : v->fit_waves_per_cu(h->N, has_lw, hl, kind == TILE_PAIR);
+    h->occ_cache.emplace_back(key, occ);
+    return occ;
 }
 
 // Lanes per block by batch size (measured on 16x16 blocks, profiles/r02/bench_shapes.txt): many blocks -> 16 lanes per
@@ -191,13 +257,13 @@ int big_block_lanes(const smoe_context* h) {
     const smoe::Variant *v64 = nullptr, *v32 = nullptr;
     for (int i = 0; i < n; ++i) {
         if (v[i].D != h->cfg.dim || v[i].C != h->cfg.channels || v[i].K != h->cfg.kernels || !variant_serves(v[i], h)) continue;
-        if (v[i].lds_bytes(h->N, false, h->cfg.quantization_mode >= 2) > 160u * 1024u) continue;
+        if (variant_lds_bytes(v[i], h, false) > 160u * 1024u) continue;
         if (v[i].G == 64) v64 = &v[i];
         if (v[i].G == 32) v32 = &v[i];
     }
     int g = 64;
     if (v64 && v32 && !h->cfg.ssim_opt && hoist_level(h, v32) >= hoist_level(h, v64) && hipSetDevice(h->cfg.device) == hipSuccess) {
-        const int occ = v64->fit_waves_per_cu(h->N, false, hoist_level(h, v64), false);
+        const int occ = fit_waves_per_cu(h, v64, TILE_PLAIN, false);
         if (occ > 0 && occ < 8) g = 32;
     }
     h->big_g = g;
@@ -230,13 +296,12 @@ constexpr int PAIR_MAX_BLOCKS = 1024;
 #ifndef SMOE_TEAM_MAX_BLOCKS
 #define SMOE_TEAM_MAX_BLOCKS 0          // automatic team tiling up to this many blocks (0: only when forced, smoe_set_tiling)
 #endif
-bool wants_pair(smoe_context* h, const smoe::Variant* v, int num_blocks) {
+bool wants_pair(const smoe_context* h, const smoe::Variant* v, int num_blocks) {
     if (v->G != 64 || v->W != 2 || h->N < 128) return false;
     if (h->cfg.ssim_opt || h->kc.qmode || h->kc.inverse_cov) return false;
     if (h->force_pair) return h->force_pair > 0;
     if (choice_blocks(h, num_blocks) > (long)PAIR_MAX_BLOCKS * h->simds / 1024) return false;     // at most one block per SIMD
-    if (h->pair_occ < 0) h->pair_occ = v->fit_waves_per_cu(h->N, false, hoist_level(h, v), true);   // of the PAIR kernel itself
-    return h->pair_occ >= 8;                                   // two wavefronts per SIMD can be resident together
+    return fit_waves_per_cu(h, v, TILE_PAIR, false) >= 8;      // of the PAIR kernel itself: two wavefronts per SIMD can be resident together
 }
 
 // SMOE_DEBUG build (make EXTRA=-DSMOE_DEBUG=1): the kernels report failed device-side checks (LDS carve-up vs the dynamic LDS of
@@ -318,14 +383,9 @@ const smoe::Variant* duo_variant(const smoe_context* h, int num_blocks, bool has
         if (h->force_duo == 0 && cb > one_per_simd) {
             // Up to one and a half blocks per SIMD -- three of the kernel's wavefronts on every SIMD, all resident at once -- it
             // still beats one wavefront per block (1 536 blocks of 16x16: 151 vs 132 Gpx-it/s, 1 280: 131 vs 112; 1 792, which
-            // needs a second round: 113 vs 148): only if the kernel's registers and LDS allow three wavefronts per SIMD.
-#if SMOE_HOST_TEST
-            return nullptr;
-#else
-            int& occ = h->duo_occ[has_lw ? 1 : 0];
-            if (occ == -2) occ = v[i].duo_waves_per_cu(h->N, has_lw, hoist_level(h, &v[i]));
-            if (occ < 12) return nullptr;
-#endif
+            // needs a second round: 113 vs 148): only if the kernel's registers and LDS allow three wavefronts per SIMD
+            // (without a device the count is unknown, -1: no).
+            if (fit_waves_per_cu(h, &v[i], TILE_DUO, has_lw) < 12) return nullptr;
         }
         return &v[i];
     }
@@ -338,7 +398,6 @@ const smoe::Variant* find_variant(const smoe_context* h, int num_blocks, bool ha
     const int want = wanted_lanes(h, choice_blocks(h, num_blocks));
     const smoe::Variant* fallback = nullptr;
     int fallback_dist = 1 << 30;
-    const bool hq = h->cfg.quantization_mode >= 2;     // the mode-2/3 fit kernels keep a quantised parameter image in LDS
     for (int i = 0; i < n; ++i) {
         if (v[i].D != h->cfg.dim || v[i].C != h->cfg.channels || v[i].K != h->cfg.kernels) continue;
         if (!variant_serves(v[i], h)) continue;
@@ -348,15 +407,63 @@ const smoe::Variant* find_variant(const smoe_context* h, int num_blocks, bool ha
             const bool b16 = h->cfg.dim == 2 && h->cfg.block_shape[0] == 16 && h->cfg.block_shape[1] == 16;
             const int g = h->force_g ? h->force_g : (b16 ? 16 : 64);
             if (v[i].G != g) continue;
-            if (v[i].lds_bytes_ssim(h->N, has_lw, h->cfg.block_shape[0], h->cfg.block_shape[1], h->cfg.block_shape[2], hq) > 160u * 1024u) continue;
-            return &v[i];
         }
-        if (v[i].lds_bytes(h->N, has_lw, hq) > 160u * 1024u) continue;
+        // (the mode-2/3 fit kernels keep a quantised parameter image in LDS, the SSIM kernels their planes)
+        if (variant_lds_bytes(v[i], h, has_lw) > 160u * 1024u) continue;
+        if (h->cfg.ssim_opt) return &v[i];
         if (v[i].G == want) return &v[i];
         const int dist = (v[i].G > want) ? (v[i].G - want) : 4 * (want - v[i].G);     // prefer the next LARGER tiling
         if (dist < fallback_dist) { fallback = &v[i]; fallback_dist = dist; }
     }
     return h->force_g ? nullptr : fallback;
+}
+
+// What smoe_fit launches for a batch: smoe_fit, smoe_fit_variant and smoe_fit_occupancy all read it from here.
+struct FitPlan {
+    const smoe::Variant* v;   // the variant that carries the launch (null: none)
+    bool launches;            // a regular variant fits this block size in LDS: smoe_fit launches nothing without one, even where
+                              // a forced duo tiling would fit (smoe_fit_variant still names that one)
+    int kind;                 // TilingKind
+    int team;                 // TILE_TEAM: wavefronts per workgroup
+    int hoist;                // hoisting level of v's tiling on this block shape
+    smoe::Graph graph;        // with pair set for TILE_PAIR
+    hipError_t device;        // of hipSetDevice (the duo and pair rules ask the device for a kernel's occupancy)
+};
+
+FitPlan plan_fit(const smoe_context* h, int num_blocks, bool has_lw) {
+    FitPlan pl = {find_variant(h, num_blocks, has_lw), false, TILE_PLAIN, 0, 0, graph_of(h), hipSuccess};
+    pl.launches = pl.v != nullptr;
+    pl.device = hipSetDevice(h->cfg.device);
+    const smoe::Variant* v16 = nullptr;
+    if (const smoe::Variant* vduo = duo_variant(h, num_blocks, has_lw)) {
+        pl.kind = TILE_DUO;
+        pl.v = vduo;
+    } else if ((pl.team = team_waves(h, num_blocks, has_lw, &v16)) > 0) {
+        pl.kind = TILE_TEAM;
+        pl.v = v16;
+    } else if (pl.v && wants_pair(h, pl.v, num_blocks)) {
+        pl.kind = TILE_PAIR;
+        pl.graph.pair = true;
+    }
+    if (pl.v) pl.hoist = hoist_level(h, pl.v);
+    return pl;
+}
+
+// The name of a plan as smoe_fit_variant spells it -- the table name, the duo and team tilings with their own suffix in
+// place of the lanes -- and, launch = true, as smoe_last_fit_variant does: with the marks of the graph and the loss weights.
+std::string plan_name(const FitPlan& pl, bool launch, bool has_lw, bool lw_is_sample) {
+    std::string nm = pl.v->name;
+    if (pl.kind == TILE_DUO || pl.kind == TILE_TEAM) {
+        const size_t g = nm.find(pl.kind == TILE_DUO ? "_g64" : "_g16");
+        if (g != std::string::npos) nm.resize(g);
+        nm += (pl.kind == TILE_DUO) ? "_duo64w2" : "_team16w" + std::to_string(pl.team);
+    }
+    if (!launch) return nm;
+    if (pl.kind == TILE_PLAIN || pl.kind == TILE_PAIR)
+        nm += pl.graph.ssim ? "+ssim" : (pl.graph.quant ? "+quant" : (pl.graph.ic ? "+ic" : (pl.graph.pair ? "_pair" : "")));
+    if (has_lw) nm += "+lw";                    // (the SSIM loss ignores the weights, but its LDS layout makes room for them)
+    if (lw_is_sample) nm += "+sample";
+    return nm;
 }
 
 }  // namespace
@@ -386,8 +493,7 @@ int smoe_padded_kernels_full(int32_t dim, int32_t channels, int32_t kernels) {
     int n = 0, best = -1;
     const smoe::Variant* v = smoe::variants(&n);
     for (int i = 0; i < n; ++i)
-        if (v[i].D == dim && v[i].C == channels && v[i].K >= kernels && v[i].fit_ssim != nullptr && v[i].fit_quant != nullptr &&
-            (best < 0 || v[i].K < best)) best = v[i].K;
+        if (v[i].D == dim && v[i].C == channels && v[i].K >= kernels && v[i].full && (best < 0 || v[i].K < best)) best = v[i].K;
     return best;
 }
 
@@ -437,28 +543,14 @@ int smoe_create(smoe_handle* out, const smoe_config* cfg) {
     if (!h) return fail(SMOE_ERR_INVALID, "smoe_create: out of host memory");
     h->cfg = *cfg;
     h->N = (int)N;
-    h->force_g = 0;
-    h->force_pair = 0;
-    h->force_team = 0;
-    h->force_duo = 0;
-    h->lw_is_sample = 0;
-    h->simds = 1024;
+    h->simds = 1024;          // (everything else starts from the zeros of the value-initialisation)
 #if !SMOE_HOST_TEST
     {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->device) == hipSuccess && cus > 0) h->simds = 4 * cus;
     }
 #endif
-    h->total_blocks = 0;
-    h->pair_occ = -1;
-    h->duo_occ[0] = h->duo_occ[1] = -2;
     h->big_g = -1;
-    h->mus_grid = nullptr;
-    h->d_coords = nullptr;
-    h->d_probes = nullptr;
-    h->d_ssim_T = nullptr;
-    h->d_partials = nullptr;
-    h->d_dbg = nullptr;
     const int D = cfg->dim;
 
     // per-pixel coordinates [D][N], 'ij' meshgrid flattened row-major (smoe.py:2418-2421,1650)
@@ -490,55 +582,14 @@ int smoe_create(smoe_handle* out, const smoe_config* cfg) {
     if (e == hipSuccess) e = dev_malloc(&h->d_dbg, sizeof(uint32_t));
     if (e == hipSuccess) e = dev_zero(h->d_dbg, sizeof(uint32_t));
 #endif
-    if (e == hipSuccess && cfg->ssim_opt) {
-        const int bh = cfg->block_shape[0], bw = cfg->block_shape[1], bt = (cfg->dim == 3) ? cfg->block_shape[2] : 0;
-        std::vector<float> tabs((size_t)11 * (bh + bw + bt));
-        ssim_axis_table(bh, tabs.data());
-        ssim_axis_table(bw, tabs.data() + (size_t)11 * bh);
-        if (bt) ssim_axis_table(bt, tabs.data() + (size_t)11 * (bh + bw));
-        e = dev_malloc(&h->d_ssim_T, sizeof(float) * tabs.size());
-        if (e == hipSuccess) e = dev_upload(h->d_ssim_T, tabs.data(), sizeof(float) * tabs.size());
-    }
+    if (e == hipSuccess && cfg->ssim_opt)
+        e = upload_ssim_tables(&h->d_ssim_T, cfg->block_shape[0], cfg->block_shape[1], (cfg->dim == 3) ? cfg->block_shape[2] : 0);
     if (e != hipSuccess) {
-        if (h->d_coords) dev_free(h->d_coords);
-        if (h->d_probes) dev_free(h->d_probes);
-        if (h->d_ssim_T) dev_free(h->d_ssim_T);
-        if (h->d_partials) dev_free(h->d_partials);
-        if (h->d_dbg) dev_free(h->d_dbg);
-        delete h;
+        smoe_destroy(h);
         return fail_hip(e, "smoe_create: workspace");
     }
 
-    smoe::KernelConsts& kc = h->kc;
-    const double two_p = std::ldexp(1.0, cfg->precision);
-    kc.tau = (float)(0.5 * 1.0 / two_p);                 // smoe.py:825
-    kc.epsm = (float)((double)cfg->margin * 1.0 / two_p); // smoe.py:931
-    const float levels = (float)(two_p - 1.0);
-    kc.scale = 1.0f / levels;                            // TF Nudge(): (max-min)/(quant_max-quant_min)
-    kc.inv_scale = 1.0f / kc.scale;
-    kc.nudged_max = fminf(1.0f, levels * kc.scale);      // combined clip_by_value(0,1) + nudged range
-    const int C = cfg->channels;
-    for (int c = 0; c < SMOE_MAX_CHANNELS; ++c) kc.cw[c] = 0.0f;
-    for (int c = 0; c < C; ++c) {
-        if (cfg->use_yuv) kc.cw[c] = (float)(((c == 0) ? 6.0 / 8.0 : 1.0 / 8.0) / (double)N);   // smoe.py:934
-        else kc.cw[c] = (float)(1.0 / ((double)N * C));                                          // smoe.py:937
-    }
-    kc.n_dis = (float)std::sqrt(std::pow(2.0 * M_PI, (double)D));                                // smoe.py:812
-    kc.inv_n_dis = 1.0f / kc.n_dis;
-    kc.use_det = cfg->use_determinant ? 1 : 0;
-    kc.train_gammas = cfg->train_gammas ? 1 : 0;
-    kc.only_y_gamma = (cfg->only_y_gamma && cfg->use_yuv && cfg->train_gammas) ? 1 : 0;   // smoe.py:725
-    for (int c = 0; c < SMOE_MAX_CHANNELS; ++c) kc.sw[c] = 0.0f;
-    for (int c = 0; c < C; ++c) {                       // smoe.py:1006-1009, mean over the bh*bw window positions
-        const double w = cfg->use_yuv ? ((c == 0) ? 6.0 / 8.0 : 1.0 / 8.0) : 1.0 / (double)C;
-        kc.sw[c] = (float)(w / (double)N);
-    }
-    fill_quant_consts(kc, cfg->quantization_mode, cfg->quantize_pis, cfg->train_musx, cfg->bit_depths,
-                      cfg->lower_bounds, cfg->upper_bounds);
-    kc.inverse_cov = cfg->train_inverse_cov ? 1 : 0;
-    kc.radial = cfg->radial_as ? 1 : 0;
-    kc.kcount_norm = cfg->kernel_count_as_norm_l1 ? 1 : 0;
-    kc.pis_l1_raw = cfg->pis_l1;
+    fill_kernel_consts(h->kc, *cfg, N);
     {
         int nv = 0;
         const smoe::Variant* vv = smoe::variants(&nv);
@@ -619,27 +670,9 @@ int smoe_set_total_blocks(smoe_handle h, int64_t total_blocks) {
 
 const char* smoe_fit_variant(smoe_handle h, int32_t num_blocks) {
     if (!h) return "";
-#if !SMOE_HOST_TEST
-    (void)hipSetDevice(h->cfg.device);       // (the duo rule asks the device for the kernel's occupancy)
-#endif
-    if (const smoe::Variant* vd = duo_variant(h, num_blocks, false)) {
-        h->variant_name = std::string(vd->name);
-        const size_t g = h->variant_name.find("_g64");
-        if (g != std::string::npos) h->variant_name.resize(g);
-        h->variant_name += "_duo64w2";
-        return h->variant_name.c_str();
-    }
-    const smoe::Variant* v16 = nullptr;
-    const int nw = team_waves(h, num_blocks, false, &v16);
-    if (nw > 0) {
-        h->variant_name = std::string(v16->name);
-        const size_t g = h->variant_name.find("_g16");
-        if (g != std::string::npos) h->variant_name.resize(g);
-        h->variant_name += "_team16w" + std::to_string(nw);
-        return h->variant_name.c_str();
-    }
-    const smoe::Variant* v = find_variant(h, num_blocks, false);
-    return v ? v->name : "";
+    const FitPlan pl = plan_fit(h, num_blocks, false);
+    h->variant_name = pl.v ? plan_name(pl, false, false, false) : std::string();
+    return h->variant_name.c_str();
 }
 
 const char* smoe_last_fit_variant(smoe_handle h) {
@@ -648,14 +681,12 @@ const char* smoe_last_fit_variant(smoe_handle h) {
 
 int smoe_fit_occupancy(smoe_handle h, int32_t num_blocks) {
     if (!h) return fail(SMOE_ERR_INVALID, "smoe_fit_occupancy: null handle");
-    const smoe::Variant* v = find_variant(h, num_blocks, false);
-    if (!v) return fail(SMOE_ERR_UNSUPPORTED, "smoe_fit_occupancy: no variant");
-    if (hipSetDevice(h->cfg.device) != hipSuccess) return fail(SMOE_ERR_HIP, "hipSetDevice");
-    if (const smoe::Variant* vd = duo_variant(h, num_blocks, false)) return vd->duo_waves_per_cu(h->N, false, hoist_level(h, vd));
-    const smoe::Variant* v16 = nullptr;
-    const int nw = team_waves(h, num_blocks, false, &v16);
-    if (nw > 0) return v16->team_waves_per_cu(h->N, false, nw);
-    return v->fit_waves_per_cu(h->N, false, hoist_level(h, v), false);
+    const FitPlan pl = plan_fit(h, num_blocks, false);
+    if (!pl.launches) return fail(SMOE_ERR_UNSUPPORTED, "smoe_fit_occupancy: no variant");
+    if (pl.device != hipSuccess) return fail(SMOE_ERR_HIP, "hipSetDevice");
+    if (pl.kind == TILE_TEAM) return pl.v->team_waves_per_cu(h->N, false, pl.team);
+    // (a pair launch is answered with the one-wavefront-per-block kernel of its tiling)
+    return fit_waves_per_cu(h, pl.v, (pl.kind == TILE_DUO) ? TILE_DUO : TILE_PLAIN, false);
 }
 
 int smoe_forward(smoe_handle h, int32_t num_blocks, const float* target, const float* loss_w,
@@ -679,10 +710,9 @@ int smoe_forward(smoe_handle h, int32_t num_blocks, const float* target, const f
     a.ssim_T = h->d_ssim_T; a.bh = h->cfg.block_shape[0]; a.bw = h->cfg.block_shape[1]; a.bt = h->cfg.block_shape[2];
     a.mus_grid = h->mus_grid;
     a.lds_floats = 0; a.dbg = h->d_dbg;
-    if (h->cfg.ssim_opt) HIP_TRY(v->fwd_ssim(a, (hipStream_t)stream), "smoe_forward (ssim) launch");
-    else if (h->kc.qmode) HIP_TRY(v->fwd_quant(a, (hipStream_t)stream), "smoe_forward (quantised) launch");
-    else if (h->kc.inverse_cov) HIP_TRY(v->fwd_ic(a, (hipStream_t)stream), "smoe_forward (inverse covariance) launch");
-    else HIP_TRY(v->fwd(a, (hipStream_t)stream), "smoe_forward launch");
+    smoe::Graph g = graph_of(h);
+    g.outs = recon != nullptr || gate_w != nullptr || argmax != nullptr;
+    HIP_TRY(v->fwd(a, g, (hipStream_t)stream), "smoe_forward launch");
     return check_debug_word(h, (hipStream_t)stream, "smoe_forward");
 }
 
@@ -695,9 +725,10 @@ int smoe_fit(smoe_handle h, int32_t num_blocks, const float* target, const float
     if (num_blocks == 0 || n_iters == 0) return SMOE_OK;
     if (!target || !params_ok(p) || !s || !params_ok(&s->m) || !params_ok(&s->v) || !active)
         return fail(SMOE_ERR_INVALID, "smoe_fit: target, params, adam state and active are required");
-    const smoe::Variant* v = find_variant(h, num_blocks, loss_w != nullptr);
-    if (!v) return fail(SMOE_ERR_UNSUPPORTED, "smoe_fit: no kernel variant fits this block size in LDS");
-    HIP_TRY(hipSetDevice(h->cfg.device), "hipSetDevice");
+    const bool has_lw = loss_w != nullptr;
+    const FitPlan pl = plan_fit(h, num_blocks, has_lw);
+    if (!pl.launches) return fail(SMOE_ERR_UNSUPPORTED, "smoe_fit: no kernel variant fits this block size in LDS");
+    HIP_TRY(pl.device, "hipSetDevice");
     const smoe_config& c = h->cfg;
     smoe::FitArgs a;
     a.target = target; a.loss_w = loss_w; a.p = *p; a.m = s->m; a.v = s->v;
@@ -710,66 +741,28 @@ int smoe_fit(smoe_handle h, int32_t num_blocks, const float* target, const float
     a.reg_pi = c.pis_l1 / (float)(c.start_pis > 0 ? c.start_pis : c.kernels);
     a.reg_u = c.u_l1;
     a.kc = h->kc;
-    const int hoist = hoist_level(h, v);
-    (void)hoist;
     a.ssim_T = h->d_ssim_T; a.bh = c.block_shape[0]; a.bw = c.block_shape[1]; a.bt = c.block_shape[2];
-    a.pair = wants_pair(h, v, num_blocks) ? 1 : 0;
+    a.pair = pl.graph.pair ? 1 : 0;
     a.mus_grid = h->mus_grid;
     a.lds_floats = 0; a.dbg = h->d_dbg; a.desc_off = 0;
-    a.lw_is_sample = (h->lw_is_sample && loss_w != nullptr && !c.ssim_opt) ? 1 : 0;
-    const smoe::Variant* v16 = nullptr;
-    const int team = team_waves(h, num_blocks, loss_w != nullptr, &v16);
-    const smoe::Variant* vduo = duo_variant(h, num_blocks, loss_w != nullptr);
+    a.lw_is_sample = (h->lw_is_sample && has_lw && !c.ssim_opt) ? 1 : 0;
     a.prio_rotate = 0;
-#if !SMOE_HOST_TEST
-    {
+    if (pl.kind != TILE_TEAM) {
         // one round = every wavefront of the launch resident at once: the wavefronts' priorities rotate (rotate_priority).
         // Occupancy of the plain kernel of the tiling (the SSIM / quantised / inverse-covariance instantiations need at least
         // as many registers: their launches are classed as one round a little too often, which costs at most 2 %)
-        long waves = 0, per_cu = 0;
-        const smoe::Variant* vo = vduo ? vduo : v;
-        const int kind = vduo ? 2 : (a.pair ? 1 : 0);
-        if (team <= 0) {
-            waves = (kind != 0) ? 2L * num_blocks : ((long)num_blocks * v->G + 63) / 64;
-            const auto key = std::make_tuple((const void*)vo, kind, (int)(loss_w != nullptr));
-            bool found = false;
-            for (const auto& e : h->occ_cache)
-                if (e.first == key) { per_cu = e.second; found = true; break; }
-            if (!found) {          // (an occupancy query per launch would cost the short launches of a small batch microseconds)
-                per_cu = vduo ? vduo->duo_waves_per_cu(h->N, loss_w != nullptr, hoist_level(h, vduo))
-                              : v->fit_waves_per_cu(h->N, loss_w != nullptr, hoist, a.pair != 0);
-                h->occ_cache.emplace_back(key, (int)per_cu);
-            }
-        }
+        const long waves = (pl.kind != TILE_PLAIN) ? 2L * num_blocks : ((long)num_blocks * pl.v->G + 63) / 64;
+        const long per_cu = fit_waves_per_cu(h, pl.v, pl.kind, has_lw);
         if (per_cu > 0 && waves <= per_cu * (long)(h->simds / 4)) a.prio_rotate = 1;
     }
-#endif
-    if (vduo) HIP_TRY(vduo->fit_duo(a, hoist_level(h, vduo), (hipStream_t)stream), "smoe_fit (duo) launch");
-    else if (team > 0) HIP_TRY(v16->fit_team(a, hoist_level(h, v16), team, (hipStream_t)stream), "smoe_fit (team) launch");
-    else if (c.ssim_opt) HIP_TRY(v->fit_ssim(a, hoist, (hipStream_t)stream), "smoe_fit (ssim) launch");
-    else if (h->kc.qmode) HIP_TRY(v->fit_quant(a, hoist, (hipStream_t)stream), "smoe_fit (quantised) launch");
-    else if (h->kc.inverse_cov) HIP_TRY(v->fit_ic(a, hoist, (hipStream_t)stream), "smoe_fit (inverse covariance) launch");
-    else HIP_TRY(v->fit(a, hoist, (hipStream_t)stream), "smoe_fit launch");
-    {
-        // a launch that came about: its name (smoe_last_fit_variant).  A failed one returned above and leaves the name of the
-        // last kernel that did run
-        std::string& nm = h->last_fit_name;
-        if (vduo || team > 0) {
-            nm = vduo ? vduo->name : v16->name;
-            const size_t g = nm.find(vduo ? "_g64" : "_g16");
-            if (g != std::string::npos) nm.resize(g);
-            if (vduo) nm += "_duo64w2";
-            else { nm += "_team16w"; nm += std::to_string(team); }
-        } else {
-            nm = v->name;
-            if (c.ssim_opt) nm += "+ssim";
-            else if (h->kc.qmode) nm += "+quant";
-            else if (h->kc.inverse_cov) nm += "+ic";
-            else if (a.pair) nm += "_pair";
-        }
-        if (loss_w != nullptr) nm += "+lw";         // (the SSIM loss ignores the weights, but its LDS layout makes room for them)
-        if (a.lw_is_sample) nm += "+sample";
-    }
+    const std::string name = plan_name(pl, true, has_lw, a.lw_is_sample != 0);
+    HIP_TRY(pl.kind == TILE_DUO    ? pl.v->fit_duo(a, pl.hoist, (hipStream_t)stream)
+            : pl.kind == TILE_TEAM ? pl.v->fit_team(a, pl.hoist, pl.team, (hipStream_t)stream)
+                                   : pl.v->fit(a, pl.graph, pl.hoist, (hipStream_t)stream),
+            ("smoe_fit launch of " + name).c_str());
+    // a launch that came about: its name (smoe_last_fit_variant).  A failed one returned above and leaves the name of the
+    // last kernel that did run
+    h->last_fit_name = name;
     // TF multiplies the beta powers after every apply (fp32 running product)
     for (int i = 0; i < n_iters; ++i) {
         s->beta1_power *= c.beta1;
@@ -1047,9 +1040,7 @@ int smoe_shared_create(smoe_shared_handle* out, const smoe_shared_config* cfg) {
         }
     }
     const size_t nacc = (size_t)cfg->kernels * h->PK + cfg->kernels;
-    h->d_axes = nullptr; h->d_probes = nullptr; h->d_racc = nullptr; h->d_ssim_T = nullptr; h->d_qrng = nullptr; h->loss_w = nullptr; h->mus_grid = nullptr;
-    h->d_part = nullptr; h->d_trained = nullptr; h->d_batch_epoch = nullptr; h->epoch = 1u;
-    h->d_bar = nullptr; h->num_cus = 0; h->fit_pending = false;
+    h->epoch = 1u;            // (the pointers and everything else start from the zeros of the value-initialisation)
 #if !SMOE_HOST_TEST
     {
         int cus = 0;
@@ -1061,7 +1052,7 @@ int smoe_shared_create(smoe_shared_handle* out, const smoe_shared_config* cfg) {
         const size_t need = smoe::shared_lds_bytes(cfg->dim, cfg->channels, cfg->kernels, h->KW) +
                             smoe::shared_ssim_lds_bytes(cfg->channels, (int)Nb, cfg->batch_shape[0], cfg->batch_shape[1], (cfg->dim == 3) ? cfg->batch_shape[2] : 0);
         if (need > 160u * 1024u) {
-            delete h;
+            smoe_shared_destroy(h);
             return fail(SMOE_ERR_UNSUPPORTED, "smoe_shared_create: ssim_opt planes of this batch size do not fit in LDS");
         }
     }
@@ -1087,57 +1078,13 @@ int smoe_shared_create(smoe_shared_handle* out, const smoe_shared_config* cfg) {
     if (e == hipSuccess) e = dev_zero(h->d_bar, sizeof(uint32_t) * h->bar_words);
     if (e == hipSuccess) e = dev_malloc(&h->d_qrng, sizeof(float) * smoe::SHARED_QRNG_FLOATS);
     if (e == hipSuccess) e = dev_zero(h->d_qrng, sizeof(float) * smoe::SHARED_QRNG_FLOATS);
-    if (e == hipSuccess && cfg->ssim_opt) {
-        const int bh = cfg->batch_shape[0], bw = cfg->batch_shape[1], bt = (cfg->dim == 3) ? cfg->batch_shape[2] : 0;
-        std::vector<float> tabs((size_t)11 * (bh + bw + bt));
-        ssim_axis_table(bh, tabs.data());
-        ssim_axis_table(bw, tabs.data() + (size_t)11 * bh);
-        if (bt) ssim_axis_table(bt, tabs.data() + (size_t)11 * (bh + bw));
-        e = dev_malloc(&h->d_ssim_T, sizeof(float) * tabs.size());
-        if (e == hipSuccess) e = dev_upload(h->d_ssim_T, tabs.data(), sizeof(float) * tabs.size());
-    }
+    if (e == hipSuccess && cfg->ssim_opt)
+        e = upload_ssim_tables(&h->d_ssim_T, cfg->batch_shape[0], cfg->batch_shape[1], (cfg->dim == 3) ? cfg->batch_shape[2] : 0);
     if (e != hipSuccess) {
-        if (h->d_axes) dev_free(h->d_axes);
-        if (h->d_probes) dev_free(h->d_probes);
-        if (h->d_racc) dev_free(h->d_racc);
-        if (h->d_ssim_T) dev_free(h->d_ssim_T);
-        if (h->d_qrng) dev_free(h->d_qrng);
-        if (h->d_part) dev_free(h->d_part);
-        if (h->d_trained) dev_free(h->d_trained);
-        if (h->d_batch_epoch) dev_free(h->d_batch_epoch);
-        if (h->d_bar) dev_free(h->d_bar);
-        delete h;
+        smoe_shared_destroy(h);
         return fail_hip(e, "smoe_shared_create: workspace");
     }
-    smoe::KernelConsts& kc = h->kc;
-    const double two_p = std::ldexp(1.0, cfg->precision);
-    kc.tau = (float)(0.5 * 1.0 / two_p);
-    kc.epsm = (float)((double)cfg->margin * 1.0 / two_p);
-    const float levels = (float)(two_p - 1.0);
-    kc.scale = 1.0f / levels;
-    kc.inv_scale = 1.0f / kc.scale;
-    kc.nudged_max = fminf(1.0f, levels * kc.scale);
-    for (int c = 0; c < SMOE_MAX_CHANNELS; ++c) kc.cw[c] = 0.0f;
-    for (int c = 0; c < C; ++c) {                                   // per-BATCH means (smoe.py:934-937)
-        if (cfg->use_yuv) kc.cw[c] = (float)(((c == 0) ? 6.0 / 8.0 : 1.0 / 8.0) / (double)Nb);
-        else kc.cw[c] = (float)(1.0 / ((double)Nb * C));
-    }
-    kc.n_dis = (float)std::sqrt(std::pow(2.0 * M_PI, (double)D));
-    kc.inv_n_dis = 1.0f / kc.n_dis;
-    kc.use_det = cfg->use_determinant ? 1 : 0;
-    kc.train_gammas = cfg->train_gammas ? 1 : 0;
-    kc.only_y_gamma = (cfg->only_y_gamma && cfg->use_yuv && cfg->train_gammas) ? 1 : 0;
-    fill_quant_consts(kc, cfg->quantization_mode, cfg->quantize_pis, cfg->train_musx, cfg->bit_depths,
-                      cfg->lower_bounds, cfg->upper_bounds);
-    for (int ch = 0; ch < SMOE_MAX_CHANNELS; ++ch) kc.sw[ch] = 0.0f;
-    for (int ch = 0; ch < C; ++ch) {                   // smoe.py:1006-1009, mean over the Nb window positions of a batch
-        const double w = cfg->use_yuv ? ((ch == 0) ? 6.0 / 8.0 : 1.0 / 8.0) : 1.0 / (double)C;
-        kc.sw[ch] = (float)(w / (double)Nb);
-    }
-    kc.inverse_cov = cfg->train_inverse_cov ? 1 : 0;
-    kc.radial = cfg->radial_as ? 1 : 0;
-    kc.kcount_norm = cfg->kernel_count_as_norm_l1 ? 1 : 0;
-    kc.pis_l1_raw = cfg->pis_l1;
+    fill_kernel_consts(h->kc, *cfg, Nb);
     *out = h;
     return SMOE_OK;
 }
@@ -1348,9 +1295,8 @@ int smoe_shared_apply(smoe_shared_handle h, smoe_params* p, smoe_adam_state* s, 
 int smoe_shared_discard(smoe_shared_handle h, void* stream) {
     if (!h) return fail(SMOE_ERR_INVALID, "smoe_shared_discard: null handle");
     HIP_TRY(hipSetDevice(h->cfg.device), "hipSetDevice");
-    const size_t nacc = (size_t)h->cfg.kernels * h->PK + h->cfg.kernels;
-    (void)nacc;
-    HIP_TRY(hipMemsetAsync(h->d_racc, 0, sizeof(double) * nacc, (hipStream_t)stream), "smoe_shared_discard");
+    HIP_TRY(hipMemsetAsync(h->d_racc, 0, sizeof(double) * ((size_t)h->cfg.kernels * h->PK + h->cfg.kernels), (hipStream_t)stream),
+            "smoe_shared_discard");
     h->epoch += 1u;
     if (h->epoch == 0u) h->epoch = 1u;
     return SMOE_OK;

@@ -148,21 +148,25 @@ struct RenderArgs {
     KernelConsts kc;
 };
 
+// The graph a fit or evaluation launch runs; with the tiling (Variant) it names one kernel instantiation
+// (resolve_fit / resolve_fwd in smoe_block.hip.h).
+struct Graph {
+    bool ssim;     // ssim_opt: loss_pixel = 1 - SSIM
+    bool quant;    // quantization_mode 2 / 3: every variable fake-quantised
+    bool ic;       // train_inverse_cov
+    bool pair;     // fit: one block on both wavefronts of a workgroup (plain graph, 64-lane tiling)
+    bool outs;     // evaluation: the launch stores recon / gate_w / argmax
+};
+
 struct Variant {
     int D, C, K, G, W;
     const char* name;
-    hipError_t (*fit)(const FitArgs&, int hoist_level, hipStream_t);
-    hipError_t (*fwd)(const FwdArgs&, hipStream_t);
-    size_t (*lds_bytes)(int N, bool has_lw, bool quant_image);
-    int (*fit_waves_per_cu)(int N, bool has_lw, int hoist_level, bool pair);   // of the kernel smoe_fit would launch
-    hipError_t (*fit_ssim)(const FitArgs&, int hoist_level, hipStream_t);   // ssim_opt (D == 2, G == 64)
-    hipError_t (*fwd_ssim)(const FwdArgs&, hipStream_t);
-    size_t (*lds_bytes_ssim)(int N, bool has_lw, int bh, int bw, int bt, bool quant_image);
+    bool full;                // built with the SSIM and quantization_mode 2 / 3 kernels (smoe_variants.def)
+    hipError_t (*fit)(const FitArgs&, Graph, int hoist_level, hipStream_t);      // hipErrorNotSupported: no kernel for the graph
+    hipError_t (*fwd)(const FwdArgs&, Graph, hipStream_t);
+    size_t (*lds_bytes)(Graph, int N, bool has_lw, int bh, int bw, int bt);      // (size_t)-1: no kernel for the graph
+    int (*fit_waves_per_cu)(int N, bool has_lw, int hoist_level, bool pair);     // of the plain / pair fit kernel
     hipError_t (*readmit_quant)(const ReadmitArgs&, const KernelConsts&, hipStream_t);   // fake-quantised graph
-    hipError_t (*fit_quant)(const FitArgs&, int hoist_level, hipStream_t);               // quantization_mode 2 / 3
-    hipError_t (*fwd_quant)(const FwdArgs&, hipStream_t);
-    hipError_t (*fit_ic)(const FitArgs&, int hoist_level, hipStream_t);                  // train_inverse_cov
-    hipError_t (*fwd_ic)(const FwdArgs&, hipStream_t);
     // team tiling (smoe_team.hip.h; entries of the 16-lane variants only): four blocks per workgroup of nw wavefronts
     hipError_t (*fit_team)(const FitArgs&, int hoist_level, int nw, hipStream_t);
     size_t (*team_lds_bytes)(int N, bool has_lw, int nw);

@@ -424,12 +424,7 @@ hipError_t launch_fit_duo(const FitArgs& a, int hoist, hipStream_t st) {
         using DT = DuoTile<D, C, K>;
         auto kern = (hoist >= 1) ? fit_duo_kernel<D, C, K, 1> : fit_duo_kernel<D, C, K, 0>;
         const size_t shm = DT::bytes(a.N, a.loss_w != nullptr, D - ((hoist >= 1) ? 1 : 0));
-        hipError_t e = allow_lds(reinterpret_cast<const void*>(kern), shm);
-        if (e != hipSuccess) return e;
-        FitArgs aa = a;
-        aa.lds_floats = (int)(shm / sizeof(float));
-        hipLaunchKernelGGL(kern, dim3(a.B), dim3(128), shm, st, aa);
-        return hipGetLastError();
+        return launch_with_lds(kern, a.B, 128, shm, a, st);
     } else {
         return hipErrorNotSupported;
     }
@@ -440,10 +435,8 @@ int duo_occupancy(int N, bool has_lw, int hoist) {
     if constexpr (DuoTile<D, C, K>::OK) {
         auto kern = (hoist >= 1) ? fit_duo_kernel<D, C, K, 1> : fit_duo_kernel<D, C, K, 0>;
         const size_t shm = DuoTile<D, C, K>::bytes(N, has_lw, D - ((hoist >= 1) ? 1 : 0));
-        int nb = 0;
-        if (allow_lds(reinterpret_cast<const void*>(kern), shm) != hipSuccess) return -1;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 128, shm) != hipSuccess) return -1;
-        return nb * 2;
+        const int nb = resident_workgroups(kern, 128, shm);
+        return (nb < 0) ? -1 : nb * 2;
     } else {
         return -1;
     }

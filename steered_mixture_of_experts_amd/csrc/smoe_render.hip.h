@@ -265,7 +265,7 @@ hipError_t launch_render(const RenderArgs& a0, int hl, int lanes, hipStream_t st
     const bool q = a.kc.qmode != 0;
     if (q && !FULL) return hipErrorNotSupported;
     if (hl > D - 1) hl = D - 1;
-    if (q && hl > 1) hl = 1;                               // as launch_fwd_quant
+    if (q && hl > 1) hl = 1;                               // as the quantised evaluation (resolve_fwd)
     void (*kern)(RenderArgs) = nullptr;
 #define SMOE_RENDER_PICK(H)                                                                                            \
     do {                                                                                                               \

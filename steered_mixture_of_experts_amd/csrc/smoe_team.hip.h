@@ -416,13 +416,7 @@ hipError_t launch_fit_team(const FitArgs& a, int hoist, int nw, hipStream_t st) 
     if (hoist < 1 || (nw != 2 && nw != 4 && nw != 8)) return hipErrorInvalidValue;
     auto kern = fit_team_kernel<D, C, K, 1, TW>;
     const size_t shm = TT::bytes(a.N, a.loss_w != nullptr, D - 1, nw);
-    hipError_t e = allow_lds(reinterpret_cast<const void*>(kern), shm);
-    if (e != hipSuccess) return e;
-    const int grid = (a.B + TT::NB - 1) / TT::NB;
-    FitArgs aa = a;
-    aa.lds_floats = (int)(shm / sizeof(float));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * nw), shm, st, aa);
-    return hipGetLastError();
+    return launch_with_lds(kern, (a.B + TT::NB - 1) / TT::NB, 64 * nw, shm, a, st);
 }
 
 template <int D, int C, int K, int TW>
@@ -430,13 +424,11 @@ int team_occupancy(int N, bool has_lw, int nw) {
     using TT = TeamTile<D, C, K>;
     auto kern = fit_team_kernel<D, C, K, 1, TW>;
     const size_t shm = TT::bytes(N, has_lw, D - 1, nw);
-    int nb = 0;
-    if (allow_lds(reinterpret_cast<const void*>(kern), shm) != hipSuccess) return -1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 64 * nw, shm) != hipSuccess) return -1;
-    return nb * nw;
+    const int nb = resident_workgroups(kern, 64 * nw, shm);
+    return (nb < 0) ? -1 : nb * nw;
 }
 
-// table entries of the 16-lane variants (SMOE_VARIANT / SMOE_VARIANT_BASIC in smoe_block.hip.h); other tilings: null
+// table entries of the 16-lane variants (SMOE_VARIANT in smoe_block.hip.h); other tilings: null
 template <int D, int C, int K, int G, int W>
 constexpr auto team_fit_ptr() -> hipError_t (*)(const FitArgs&, int, int, hipStream_t) {
     if constexpr (G == 16) return &launch_fit_team<D, C, K, W>;

@@ -25,10 +25,10 @@ namespace smoe {
 // host function (a namespace-scope table of host function pointers would also be emitted for the device)
 const Variant* SMOE_CAT(variants_d, SMOE_D, c, SMOE_C, k, SMOE_K, )(int* count) {
 #if SMOE_FULL
-    static const Variant table[] = { SMOE_VARIANT(SMOE_D, SMOE_C, SMOE_K, 16, SMOE_W16), SMOE_VARIANT_BASIC(SMOE_D, SMOE_C, SMOE_K, 32, 2),
-                                     SMOE_VARIANT(SMOE_D, SMOE_C, SMOE_K, 64, 2) };
+    static const Variant table[] = { SMOE_VARIANT(SMOE_D, SMOE_C, SMOE_K, 16, SMOE_W16, 1), SMOE_VARIANT(SMOE_D, SMOE_C, SMOE_K, 32, 2, 0),
+                                     SMOE_VARIANT(SMOE_D, SMOE_C, SMOE_K, 64, 2, 1) };
 #else
-    static const Variant table[] = { SMOE_VARIANT_BASIC(SMOE_D, SMOE_C, SMOE_K, 16, SMOE_W16), SMOE_VARIANT_BASIC(SMOE_D, SMOE_C, SMOE_K, 64, 2) };
+    static const Variant table[] = { SMOE_VARIANT(SMOE_D, SMOE_C, SMOE_K, 16, SMOE_W16, 0), SMOE_VARIANT(SMOE_D, SMOE_C, SMOE_K, 64, 2, 0) };
 #endif
     *count = (int)(sizeof(table) / sizeof(table[0]));
     return table;

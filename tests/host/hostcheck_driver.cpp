@@ -15,6 +15,9 @@
 #include "smoe_hip.h"
 
 static int g_checks = 0, g_fail = 0;
+// --dump: one line per (config, tiling, total_blocks, B, loss weights) of the matrix drive_handle walks, with the decisions of
+// the host layer for it; compared between two builds of the library (nothing is committed as a golden file)
+static bool g_dump = false;
 #define EXPECT(cond)                                                                   \
     do {                                                                               \
         ++g_checks;                                                                    \
@@ -68,6 +71,16 @@ static void check_create_refusals() {
     EXPECT(smoe_destroy(nullptr) == SMOE_OK);
 }
 
+// what smoe_last_fit_variant reports without the marks of the graph and the loss weights ("+ssim", "+lw", ..., "_pair"): the
+// tiling's name as smoe_fit_variant spells it
+static std::string strip_launch_marks(std::string n) {
+    const size_t plus = n.find('+');
+    if (plus != std::string::npos) n.resize(plus);
+    const std::string pair = "_pair";
+    if (n.size() >= pair.size() && n.compare(n.size() - pair.size(), pair.size(), pair) == 0) n.resize(n.size() - pair.size());
+    return n;
+}
+
 // every entry point of one handle, up to the launch
 static void drive_handle(const smoe_config& c, bool expect_variant) {
     smoe_handle h = nullptr;
@@ -88,16 +101,27 @@ static void drive_handle(const smoe_config& c, bool expect_variant) {
         for (long long total : {0LL, 1LL, 4050LL, 32400LL, 1LL << 40}) {
             EXPECT(smoe_set_total_blocks(h, total) == SMOE_OK);
             for (int B : blocks) {
-                const char* name = smoe_fit_variant(h, B);
-                EXPECT(name != nullptr);
-                if (expect_variant && t == 0) EXPECT(std::strlen(name) > 4);
-                if (total > 0) EXPECT(std::string(name) == std::string(smoe_fit_variant(h, 1)));     // partition invariance of the choice
-                (void)smoe_fit_occupancy(h, B);            // no device: an error code, never a crash
-                // launches: everything up to the launch itself
-                const int f = smoe_fit(h, B, dummy, (B & 1) ? dummy : nullptr, &p, &st, 3, dummy, dummy, udummy, udummy, dummy, nullptr);
-                const int e = smoe_forward(h, B, dummy, nullptr, &p, dummy, bdummy, dummy, dummy, dummy, udummy, 1, nullptr);
-                EXPECT((f == SMOE_OK || f == SMOE_ERR_UNSUPPORTED) && (e == SMOE_OK || e == SMOE_ERR_UNSUPPORTED));
-                if (expect_variant && t == 0) EXPECT(f == SMOE_OK && e == SMOE_OK);
+                const char* cname = smoe_fit_variant(h, B);
+                EXPECT(cname != nullptr);
+                const std::string name = cname ? cname : "";
+                if (expect_variant && t == 0) EXPECT(name.size() > 4);
+                if (total > 0) EXPECT(name == std::string(smoe_fit_variant(h, 1)));     // partition invariance of the choice
+                const int occ = smoe_fit_occupancy(h, B);  // no device: an error code, never a crash
+                // launches: everything up to the launch itself (--dump: with and without loss weights)
+                for (int lw = g_dump ? 0 : (B & 1); lw <= (g_dump ? 1 : (B & 1)); ++lw) {
+                    const int f = smoe_fit(h, B, dummy, lw ? dummy : nullptr, &p, &st, 3, dummy, dummy, udummy, udummy, dummy, nullptr);
+                    const std::string last = smoe_last_fit_variant(h);
+                    const int e = smoe_forward(h, B, dummy, lw ? dummy : nullptr, &p, dummy, bdummy, dummy, dummy, dummy, udummy, 1, nullptr);
+                    EXPECT((f == SMOE_OK || f == SMOE_ERR_UNSUPPORTED) && (e == SMOE_OK || e == SMOE_ERR_UNSUPPORTED));
+                    if (expect_variant && t == 0) EXPECT(f == SMOE_OK && e == SMOE_OK);
+                    // the launch and the query name the same tiling
+                    if (f == SMOE_OK && !lw) EXPECT(strip_launch_marks(last) == name);
+                    if (g_dump)
+                        std::printf("d%dc%dk%d %dx%dx%d qp%d ic%d rad%d qm%d ssim%d | t%d total%lld B%d lw%d | %s | occ %d fit %d fwd %d | %s\n",
+                                    c.dim, c.channels, c.kernels, c.block_shape[0], c.block_shape[1], c.block_shape[2], c.quantize_pis,
+                                    c.train_inverse_cov, c.radial_as, c.quantization_mode, c.ssim_opt, t, total, B, lw, name.c_str(), occ, f, e,
+                                    last.c_str());
+                }
             }
         }
     }
@@ -178,14 +202,17 @@ static void check_variant_tables() {
         for (int N : {1, 35, 256, 1000, 1024, 4096, 8192})
             for (int lw = 0; lw < 2; ++lw)
                 for (int hq = 0; hq < 2; ++hq) {
-                    const size_t b = v[i].lds_bytes(N, lw != 0, hq != 0);
+                    smoe::Graph g = {}, gs = {};
+                    g.quant = gs.quant = hq != 0;
+                    gs.ssim = true;
+                    const size_t b = v[i].lds_bytes(g, N, lw != 0, 0, 0, 0);
                     EXPECT(b > 0 && b < (size_t)1 << 31 && (b & 3) == 0);
                     EXPECT(b >= sizeof(float) * (size_t)(v[i].C * N * (64 / v[i].G) * v[i].W));     // at least the staged targets
-                    if (lw) EXPECT(b >= v[i].lds_bytes(N, false, hq != 0));
-                    if (v[i].lds_bytes_ssim) {
-                        const size_t s2 = v[i].lds_bytes_ssim(256, lw != 0, 16, 16, 0, hq != 0);
-                        const size_t s3 = v[i].lds_bytes_ssim(1024, lw != 0, 16, 16, 4, hq != 0);
-                        EXPECT(s2 == (size_t)-1 || s2 > v[i].lds_bytes(256, lw != 0, hq != 0));
+                    if (lw) EXPECT(b >= v[i].lds_bytes(g, N, false, 0, 0, 0));
+                    if (v[i].full) {
+                        const size_t s2 = v[i].lds_bytes(gs, 256, lw != 0, 16, 16, 0);
+                        const size_t s3 = v[i].lds_bytes(gs, 1024, lw != 0, 16, 16, 4);
+                        EXPECT(s2 == (size_t)-1 || s2 > v[i].lds_bytes(g, 256, lw != 0, 0, 0, 0));
                         EXPECT(s3 == (size_t)-1 || s3 > 0);
                     }
                     if (v[i].team_lds_bytes)
@@ -274,7 +301,8 @@ static void check_shared() {
     EXPECT(smoe_shared_num_batches(nullptr) == SMOE_ERR_INVALID);
 }
 
-int main() {
+int main(int argc, char** argv) {
+    g_dump = argc > 1 && std::strcmp(argv[1], "--dump") == 0;
     check_create_refusals();
     check_variant_tables();
     check_block_handles();
