@@ -251,5 +251,5 @@ def synthetic_blocks(B: int, block_shape: Sequence[int], C: int, seed: int) -> n
 
 
 def psnr(mse, precision):
-    """plotter.py:14-15."""
+    """plotter.py:14-15: mse is mse_op, i.e. mean(diff^2) * (2^p)^2 (smoe.py:1053)."""
     return 10 * np.log10((2 ** precision) ** 2 / mse)

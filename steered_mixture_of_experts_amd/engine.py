@@ -16,11 +16,10 @@ from . import _lib
 PARAM_NAMES = ("pis", "musX", "A_diagonal", "A_corr", "gamma_e", "nu_e")
 
 
-@dataclasses.dataclass
-class EngineConfig:
-    """Mirror of ``smoe_config`` (include/smoe_hip.h); defaults = smoe_test.py CLI defaults
-    with kernel adding off (smoe_test.py:262-352)."""
-    block_shape: Sequence[int]
+@dataclasses.dataclass(kw_only=True)
+class _CommonConfig:
+    """The fields ``smoe_config`` and ``smoe_shared_config`` (include/smoe_hip.h) share; defaults = smoe_test.py CLI
+    defaults with kernel adding off (smoe_test.py:262-352).  Keyword-only: the modes put their shapes in front."""
     channels: int
     kernels: int
     precision: int = 8
@@ -50,7 +49,13 @@ class EngineConfig:
     upper_bounds: Sequence[float] = (2500, 1.3, 5, 2, 32)
     train_inverse_cov: bool = False      # smoe.py:734-735,791-793 (reference ctor default True, CLI default False)
     radial_as: bool = False              # smoe.py:714-719: equal steering diagonals, tied gradient, A_corr untrained
-    kernel_count_as_norm_l1: bool = False  # smoe.py:1022-1027
+    kernel_count_as_norm_l1: bool = False  # smoe.py:1022-1027: pis_l1 / count(qpis > 0)
+
+
+@dataclasses.dataclass(kw_only=True)
+class EngineConfig(_CommonConfig):
+    """Mirror of ``smoe_config``: every block of ``block_shape`` pixels is its own model."""
+    block_shape: Sequence[int]
 
     @property
     def dim(self) -> int:
@@ -62,6 +67,47 @@ class EngineConfig:
         for s in self.block_shape:
             n *= int(s)
         return n
+
+
+@dataclasses.dataclass(kw_only=True)
+class SharedConfig(_CommonConfig):
+    """Mirror of ``smoe_shared_config``: ONE global kernel set over the image, batches of
+    ``batch_shape`` pixels with per-batch kernel lists."""
+    image_shape: Sequence[int]
+    batch_shape: Sequence[int]
+    overlap: int = 0
+
+    @property
+    def dim(self) -> int:
+        return len(self.image_shape)
+
+
+_AS_IS = ("channels", "kernels", "precision", "margin", "lr_expert", "lr_pis", "lr_steer", "beta1", "beta2", "adam_eps",
+          "pis_l1", "u_l1")
+_AS_INT = ("use_determinant", "use_yuv", "train_pis", "train_gammas", "train_musx", "only_y_gamma", "ssim_opt",
+           "quantization_mode", "quantize_pis", "train_inverse_cov", "radial_as", "kernel_count_as_norm_l1")
+
+
+def marshal_common(c, cfg: _CommonConfig):
+    """Fill the fields a ``_lib.SmoeConfig`` / ``_lib.SmoeSharedConfig`` ``c`` takes from ``_CommonConfig`` (and ``dim``).
+    The shapes, ``abi_version`` and ``device`` are the engine constructor's.  Pure ctypes: no device, no library."""
+    c.dim = cfg.dim
+    for name in _AS_IS:
+        setattr(c, name, getattr(cfg, name))
+    for name in _AS_INT:
+        setattr(c, name, int(getattr(cfg, name)))
+    c.grad_clip = cfg.grad_clip or 0.0
+    c.start_pis = cfg.start_pis or cfg.kernels
+    for i in range(5):
+        c.bit_depths[i] = int(cfg.bit_depths[i])
+        c.lower_bounds[i], c.upper_bounds[i] = float(cfg.lower_bounds[i]), float(cfg.upper_bounds[i])
+    return c
+
+
+def _shape3(dst, shape, d):
+    """The first ``d`` entries of ``shape`` into a three-slot struct field, 1 for the axes the model does not have."""
+    for i in range(3):
+        dst[i] = int(shape[i]) if i < d else 1
 
 
 def param_shapes(B: int, K: int, d: int, Cc: int) -> Dict[str, tuple]:
@@ -90,45 +136,27 @@ class AdamState:
         return int(self.c.step)
 
 
-class BlockEngine:
-    def __init__(self, cfg: EngineConfig, device: Optional[torch.device] = None):
+def _slots(ctype, values, fill):
+    """A three-slot ctypes array: one entry per axis, ``fill`` for the axes the model does not have."""
+    values = list(values)
+    return (ctype * 3)(*(values + [fill] * (3 - len(values))))
+
+
+class _Engine:
+    """What the two engines share: library and device, the handle's life, the stream, the Adam slots and the argument
+    plumbing of ``render``."""
+    _name = _destroy = None        # the subclass's public name and the entry point that frees its handle
+
+    def _open(self, cfg, device):
         self.lib = _lib.load()
         if not torch.cuda.is_available():
-            raise RuntimeError("BlockEngine needs a HIP device; this package has no CPU path")
+            raise RuntimeError(f"{self._name} needs a HIP device; this package has no CPU path")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.cfg = cfg
-        c = _lib.SmoeConfig()
-        c.abi_version = _lib.SMOE_ABI_VERSION
-        c.device = self.device.index or 0
-        c.dim = cfg.dim
-        shape = list(cfg.block_shape) + [1] * (3 - cfg.dim)
-        for i in range(3):
-            c.block_shape[i] = int(shape[i])
-        c.channels, c.kernels, c.precision = cfg.channels, cfg.kernels, cfg.precision
-        c.margin = cfg.margin
-        c.use_determinant, c.use_yuv = int(cfg.use_determinant), int(cfg.use_yuv)
-        c.train_pis, c.train_gammas, c.train_musx = int(cfg.train_pis), int(cfg.train_gammas), int(cfg.train_musx)
-        c.lr_expert, c.lr_pis, c.lr_steer = cfg.lr_expert, cfg.lr_pis, cfg.lr_steer
-        c.beta1, c.beta2, c.adam_eps = cfg.beta1, cfg.beta2, cfg.adam_eps
-        c.grad_clip = cfg.grad_clip or 0.0
-        c.pis_l1, c.u_l1 = cfg.pis_l1, cfg.u_l1
-        c.start_pis = cfg.start_pis or cfg.kernels
-        c.only_y_gamma = int(cfg.only_y_gamma)
-        c.ssim_opt = int(cfg.ssim_opt)
-        c.quantization_mode, c.quantize_pis = int(cfg.quantization_mode), int(cfg.quantize_pis)
-        for i in range(5):
-            c.bit_depths[i] = int(cfg.bit_depths[i])
-            c.lower_bounds[i], c.upper_bounds[i] = float(cfg.lower_bounds[i]), float(cfg.upper_bounds[i])
-        c.train_inverse_cov = int(cfg.train_inverse_cov)
-        c.radial_as = int(cfg.radial_as)
-        c.kernel_count_as_norm_l1 = int(cfg.kernel_count_as_norm_l1)
-        self._c = c
-        self._h = C.c_void_p()
-        _lib.check(self.lib.smoe_create(C.byref(self._h), C.byref(c)))
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
-            self.lib.smoe_destroy(self._h)
+            getattr(self.lib, self._destroy)(self._h)
             self._h = None
 
     def __del__(self):
@@ -137,10 +165,46 @@ class BlockEngine:
         except Exception:
             pass
 
-    # -- helpers ---------------------------------------------------------------
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
+    def new_adam_state(self, params: Dict[str, torch.Tensor]) -> AdamState:
+        return AdamState(params, self.cfg.beta1, self.cfg.beta2)
+
+    # -- render plumbing -----------------------------------------------------------
+    @staticmethod
+    def _check_render_dtype(dtype):
+        if dtype not in (torch.float32, torch.uint8):
+            raise ValueError("render: dtype must be torch.float32 or torch.uint8")
+
+    def _is_axis_table(self, t) -> bool:
+        return t.dim() == 1 and t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device
+
+    def _render_out(self, out, extent, dtype, everything: bool):
+        """The image ``[*extent, C]`` to render into: ``out`` checked, or a new one (zero-filled unless the call renders
+        ``everything``), and the pixel format constant of ``dtype``."""
+        shape = tuple(extent) + (self.cfg.channels,)
+        if out is None:
+            out = (torch.empty if everything else torch.zeros)(shape, dtype=dtype, device=self.device)
+        elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"render: out must be a contiguous {dtype} tensor {shape} on {self.device}")
+        return out, (_lib.SMOE_IMAGE_U8 if dtype == torch.uint8 else _lib.SMOE_IMAGE_F32)
+
+
+class BlockEngine(_Engine):
+    _name, _destroy = "BlockEngine", "smoe_destroy"
+
+    def __init__(self, cfg: EngineConfig, device: Optional[torch.device] = None):
+        self._open(cfg, device)
+        c = marshal_common(_lib.SmoeConfig(), cfg)
+        c.abi_version = _lib.SMOE_ABI_VERSION
+        c.device = self.device.index or 0
+        _shape3(c.block_shape, cfg.block_shape, cfg.dim)
+        self._c = c
+        self._h = C.c_void_p()
+        _lib.check(self.lib.smoe_create(C.byref(self._h), C.byref(c)))
+
+    # -- helpers ---------------------------------------------------------------
     def _check_params(self, p: Dict[str, torch.Tensor], B: int):
         shapes = param_shapes(B, self.cfg.kernels, self.cfg.dim, self.cfg.channels)
         for name in PARAM_NAMES:
@@ -169,9 +233,6 @@ class BlockEngine:
     def new_params(self, B: int) -> Dict[str, torch.Tensor]:
         shapes = param_shapes(B, self.cfg.kernels, self.cfg.dim, self.cfg.channels)
         return {k: torch.zeros(s, dtype=torch.float32, device=self.device) for k, s in shapes.items()}
-
-    def new_adam_state(self, params: Dict[str, torch.Tensor]) -> AdamState:
-        return AdamState(params, self.cfg.beta1, self.cfg.beta2)
 
     def coords(self) -> torch.Tensor:
         out = torch.empty((self.cfg.dim, self.cfg.pixels), dtype=torch.float32)
@@ -236,15 +297,14 @@ class BlockEngine:
         full-size image to render into (only the positions of the rendered blocks are written); otherwise a new one,
         zero-filled where this call renders only a part.  Returns the image, with ``want_argmax`` also the uint8 kernel
         map ``[*extent]`` (255: no kernel has influence; 255 as well where no block was rendered)."""
-        d, Cc = self.cfg.dim, self.cfg.channels
+        d = self.cfg.dim
         B = int(params["pis"].shape[0])
         self._check_params(params, B)
-        if dtype not in (torch.float32, torch.uint8):
-            raise ValueError("render: dtype must be torch.float32 or torch.uint8")
+        self._check_render_dtype(dtype)
         if len(axes) != d or len(grid) != d or len(extent) != d:
             raise ValueError(f"render: axes, grid and extent need {d} entries")
         for t in axes:
-            if t.dim() != 1 or t.numel() < 1 or t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
+            if t.numel() < 1 or not self._is_axis_table(t):
                 raise ValueError(f"render: every axis table must be a contiguous 1-d float32 tensor on {self.device}")
         grid = [int(g) for g in grid]
         extent = [int(e) for e in extent]
@@ -253,22 +313,14 @@ class BlockEngine:
             total *= g
         if active is not None and (tuple(active.shape) != (B,) or active.dtype != torch.int32 or active.device != self.device):
             raise ValueError(f"render: active must be int32 [{B}] on {self.device}")
-        shape = tuple(extent) + (Cc,)
-        if out is None:
-            out = (torch.empty if (first_block == 0 and B == total) else torch.zeros)(shape, dtype=dtype, device=self.device)
-        elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or out.device != self.device:
-            raise ValueError(f"render: out must be a contiguous {dtype} tensor {shape} on {self.device}")
-        am = None
-        if want_argmax:
-            am = torch.full(tuple(extent), 255, dtype=torch.uint8, device=self.device)
+        out, fmt = self._render_out(out, extent, dtype, everything=(first_block == 0 and B == total))
+        am = torch.full(tuple(extent), 255, dtype=torch.uint8, device=self.device) if want_argmax else None
         if B > 0:
             cp = self._cparams(params)
-            tabs = (C.c_void_p * 3)(*([t.data_ptr() for t in axes] + [None] * (3 - d)))
-            m3 = (C.c_int32 * 3)(*([int(t.numel()) for t in axes] + [1] * (3 - d)))
-            g3 = (C.c_int32 * 3)(*(grid + [1] * (3 - d)))
-            e3 = (C.c_int64 * 3)(*(extent + [1] * (3 - d)))
-            fmt = _lib.SMOE_IMAGE_U8 if dtype == torch.uint8 else _lib.SMOE_IMAGE_F32
-            _lib.check(self.lib.smoe_render(self._h, int(first_block), B, C.byref(cp), _ptr(active), tabs, m3, g3, e3,
+            tabs = _slots(C.c_void_p, [t.data_ptr() for t in axes], None)
+            m3 = _slots(C.c_int32, [int(t.numel()) for t in axes], 1)
+            _lib.check(self.lib.smoe_render(self._h, int(first_block), B, C.byref(cp), _ptr(active), tabs, m3,
+                                            _slots(C.c_int32, grid, 1), _slots(C.c_int64, extent, 1),
                                             _ptr(out), fmt, _ptr(am), self._stream()))
         return (out, am) if want_argmax else out
 
@@ -339,80 +391,18 @@ class BlockEngine:
 # =====================================================================================================
 # shared-kernel image mode
 # =====================================================================================================
-@dataclasses.dataclass
-class SharedConfig:
-    """Mirror of ``smoe_shared_config``: ONE global kernel set over the image, batches of
-    ``batch_shape`` pixels with per-batch kernel lists."""
-    image_shape: Sequence[int]
-    batch_shape: Sequence[int]
-    channels: int
-    kernels: int
-    precision: int = 8
-    margin: float = 0.5
-    use_determinant: bool = True
-    use_yuv: bool = False
-    train_pis: bool = True
-    train_gammas: bool = True
-    train_musx: bool = True
-    lr_expert: float = 1e-3
-    lr_pis: float = 1e-5
-    lr_steer: float = 1.0
-    beta1: float = 0.9
-    beta2: float = 0.999
-    adam_eps: float = 1e-8
-    grad_clip: float = 0.0
-    pis_l1: float = 0.0
-    u_l1: float = 0.0
-    start_pis: int = 0
-    only_y_gamma: bool = False
-    overlap: int = 0
-    ssim_opt: bool = False
-    train_inverse_cov: bool = False
-    radial_as: bool = False
-    kernel_count_as_norm_l1: bool = False  # smoe.py:1022-1027: pis_l1 / count(qpis > 0) over the image
-    quantization_mode: int = 0
-    quantize_pis: bool = False
-    bit_depths: Sequence[int] = (20, 18, 6, 10, 10)
-    lower_bounds: Sequence[float] = (-2500, -.3, -5, 0, -32)
-    upper_bounds: Sequence[float] = (2500, 1.3, 5, 2, 32)
-
-    @property
-    def dim(self) -> int:
-        return len(self.image_shape)
-
-
-class SharedEngine:
+class SharedEngine(_Engine):
     """Host wrapper of the smoe_shared_* entry points.  Parameters: dict of contiguous float32
     device tensors in the get_params() layout with leading K (no block axis)."""
+    _name, _destroy = "SharedEngine", "smoe_shared_destroy"
 
     def __init__(self, cfg: SharedConfig, device: Optional[torch.device] = None):
-        self.lib = _lib.load()
-        if not torch.cuda.is_available():
-            raise RuntimeError("SharedEngine needs a HIP device; this package has no CPU path")
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.cfg = cfg
-        c = _lib.SmoeSharedConfig()
-        c.abi_version, c.device, c.dim = _lib.SMOE_ABI_VERSION, self.device.index or 0, cfg.dim
-        for i in range(3):
-            c.image_shape[i] = int(cfg.image_shape[i]) if i < cfg.dim else 1
-            c.batch_shape[i] = int(cfg.batch_shape[i]) if i < cfg.dim else 1
-        c.channels, c.kernels, c.precision, c.margin = cfg.channels, cfg.kernels, cfg.precision, cfg.margin
-        c.use_determinant, c.use_yuv = int(cfg.use_determinant), int(cfg.use_yuv)
-        c.train_pis, c.train_gammas, c.train_musx = int(cfg.train_pis), int(cfg.train_gammas), int(cfg.train_musx)
-        c.lr_expert, c.lr_pis, c.lr_steer = cfg.lr_expert, cfg.lr_pis, cfg.lr_steer
-        c.beta1, c.beta2, c.adam_eps = cfg.beta1, cfg.beta2, cfg.adam_eps
-        c.grad_clip, c.pis_l1, c.u_l1 = cfg.grad_clip or 0.0, cfg.pis_l1, cfg.u_l1
-        c.start_pis = cfg.start_pis or cfg.kernels
-        c.only_y_gamma = int(cfg.only_y_gamma)
+        self._open(cfg, device)
+        c = marshal_common(_lib.SmoeSharedConfig(), cfg)
+        c.abi_version, c.device = _lib.SMOE_ABI_VERSION, self.device.index or 0
+        _shape3(c.image_shape, cfg.image_shape, cfg.dim)
+        _shape3(c.batch_shape, cfg.batch_shape, cfg.dim)
         c.overlap = int(cfg.overlap)
-        c.ssim_opt = int(cfg.ssim_opt)
-        c.train_inverse_cov = int(cfg.train_inverse_cov)
-        c.radial_as = int(cfg.radial_as)
-        c.kernel_count_as_norm_l1 = int(cfg.kernel_count_as_norm_l1)
-        c.quantization_mode, c.quantize_pis = int(cfg.quantization_mode), int(cfg.quantize_pis)
-        for i in range(5):
-            c.bit_depths[i] = int(cfg.bit_depths[i])
-            c.lower_bounds[i], c.upper_bounds[i] = float(cfg.lower_bounds[i]), float(cfg.upper_bounds[i])
         self._h = C.c_void_p()
         _lib.check(self.lib.smoe_shared_create(C.byref(self._h), C.byref(c)))
         self.num_batches = int(self.lib.smoe_shared_num_batches(self._h))
@@ -420,20 +410,6 @@ class SharedEngine:
         self.batch_pixels = 1
         for b in cfg.batch_shape:
             self.batch_pixels *= int(b)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            self.lib.smoe_shared_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _cparams(self, p):
         shapes = param_shapes(1, self.cfg.kernels, self.cfg.dim, self.cfg.channels)
@@ -453,9 +429,6 @@ class SharedEngine:
         if K % 32:
             words[:, KW - 1] = (1 << (K % 32)) - 1
         return words
-
-    def new_adam_state(self, params):
-        return AdamState(params, self.cfg.beta1, self.cfg.beta2)
 
     def _check_target(self, target, nb):
         want = (nb, self.cfg.channels, self.batch_pixels)
@@ -486,9 +459,8 @@ class SharedEngine:
         rendered batches are written); otherwise a new one, zero-filled where this call renders only a part.  Returns the
         image, with ``want_argmax`` also the int32 map ``[*E]`` of global kernel ids (-1: no kernel has influence on the
         sample; -1 as well where no batch was rendered)."""
-        d, Cc = self.cfg.dim, self.cfg.channels
-        if dtype not in (torch.float32, torch.uint8):
-            raise ValueError("render: dtype must be torch.float32 or torch.uint8")
+        d = self.cfg.dim
+        self._check_render_dtype(dtype)
         if len(axes) != d or len(samples) != d:
             raise ValueError(f"render: axes and samples need {d} entries")
         samples = [int(m) for m in samples]
@@ -497,7 +469,7 @@ class SharedEngine:
         grid = [int(s) // int(b) for s, b in zip(self.cfg.image_shape, self.cfg.batch_shape)]
         extent = [g * m for g, m in zip(grid, samples)]
         for t, e in zip(axes, extent):
-            if t.dim() != 1 or t.numel() != e or t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
+            if not self._is_axis_table(t) or t.numel() != e:
                 raise ValueError(f"render: every axis table must be a contiguous 1-d float32 tensor on {self.device} with "
                                  f"grid * samples entries ({extent})")
         if lists is not None:
@@ -509,19 +481,13 @@ class SharedEngine:
             nb = self.num_batches - int(first_batch) if num_batches is None else int(num_batches)
         if first_batch < 0 or nb < 0 or first_batch + nb > self.num_batches:
             raise ValueError("render: batch range out of bounds")
-        shape = tuple(extent) + (Cc,)
-        if out is None:
-            out = (torch.empty if nb == self.num_batches else torch.zeros)(shape, dtype=dtype, device=self.device)
-        elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or out.device != self.device:
-            raise ValueError(f"render: out must be a contiguous {dtype} tensor {shape} on {self.device}")
+        out, fmt = self._render_out(out, extent, dtype, everything=(nb == self.num_batches))
         am = torch.full(tuple(extent), -1, dtype=torch.int32, device=self.device) if want_argmax else None
         if nb > 0:
             cp = self._cparams(params)
-            tabs = (C.c_void_p * 3)(*([t.data_ptr() for t in axes] + [None] * (3 - d)))
-            m3 = (C.c_int32 * 3)(*(samples + [1] * (3 - d)))
-            fmt = _lib.SMOE_IMAGE_U8 if dtype == torch.uint8 else _lib.SMOE_IMAGE_F32
-            _lib.check(self.lib.smoe_shared_render(self._h, int(first_batch), nb, C.byref(cp), _ptr(lists), tabs, m3,
-                                                   _ptr(out), fmt, _ptr(am), self._stream()))
+            tabs = _slots(C.c_void_p, [t.data_ptr() for t in axes], None)
+            _lib.check(self.lib.smoe_shared_render(self._h, int(first_batch), nb, C.byref(cp), _ptr(lists), tabs,
+                                                   _slots(C.c_int32, samples, 1), _ptr(out), fmt, _ptr(am), self._stream()))
         return (out, am) if want_argmax else out
 
     def accumulate(self, target, params, lists, first_batch=0, loss_out=None, sse_out=None):

@@ -32,7 +32,7 @@ import torch
 
 from . import blocks as blk
 from . import dist as sdist
-from .engine import PARAM_NAMES, EngineConfig
+from .engine import PARAM_NAMES, EngineConfig, SharedConfig
 
 
 class Adam:
@@ -170,7 +170,248 @@ def _train_loop(m, num_iter, val_iter, ukl_iter, pis_l1, u_l1, callbacks, chunk_
         print("best loss/mse: ", m.best_loss, "/", m.best_mse)
 
 
-class Smoe:
+class _SmoeBase:
+    """What the two facades share: the optimizer and engine bookkeeping, the getters and ``render``.  A mode supplies
+    ``run_batched``, the hooks of ``_train_loop`` and the hooks named below."""
+    _unit = None                    # "block" / "batch": what the mode calls a tile of the image in its messages
+    _block_local_ids = False        # the engine's render() numbers the kernels per tile, 255 = none (else globally, -1)
+
+    # -- constructor pieces -------------------------------------------------------------------
+    def _set_quantizer(self, quantization_mode, quantize_pis, bit_depths, lower_bounds, upper_bounds):
+        if quantization_mode not in (0, 1, 2, 3):
+            raise ValueError("quantization_mode must be 0, 1, 2 or 3")                # smoe_test.py:298-301
+        self.quantization_mode = int(quantization_mode)
+        self.quantize_pis = bool(quantize_pis) or quantization_mode >= 2               # smoe_test.py:36-37, smoe.py:474
+        # bit depths / bounds in the order A, musX, nu_e, pis, gamma_e; None -> the CLI defaults (smoe_test.py:302-309)
+        self.bit_depths = [20, 18, 6, 10, 10] if bit_depths is None else list(bit_depths)
+        self.lower_bounds = [-2500, -.3, -5, 0, -32] if lower_bounds is None else list(lower_bounds)
+        self.upper_bounds = [2500, 1.3, 5, 2, 32] if upper_bounds is None else list(upper_bounds)
+
+    def _set_image(self, image, precision, margin, use_yuv, only_y_gamma):
+        self.image = image = np.asarray(image, dtype=np.float32)
+        self.dim_domain = image.ndim - 1                                # smoe.py:227
+        self.num_pixel = int(np.prod(image.shape[:self.dim_domain]))    # smoe.py:228
+        self.channels = image.shape[-1]
+        self.precision, self.margin = precision, margin
+        self.use_yuv = bool(use_yuv) and image.shape[-1] == 3           # smoe_test.py:41-44
+        self.only_y_gamma = bool(only_y_gamma) and self.use_yuv         # smoe_test.py:43-44, smoe.py:725-729
+        return image
+
+    def _batch_shape(self, batch_size, start_batches):
+        """smoe.py:231-247: the tile shape from ``batch_size``, or from the desired number of batches (1 -> the image)."""
+        image, d = self.image, self.dim_domain
+        if batch_size is None or batch_size[0] is None:
+            return blk.get_batch_shape(start_batches, tuple(image.shape[:d]) + (d + image.shape[-1],))[:-1]   # smoe.py:229,243
+        if len(batch_size) == d:
+            return tuple(int(b) for b in batch_size)
+        if len(batch_size) == 1:
+            return tuple(int(batch_size[0]) for _ in range(d))
+        raise ValueError("Required BatchSize doesn't fit to input dimension")    # smoe.py:237
+
+    def _reset_histories(self, iter_offset):
+        """smoe.py:183-199."""
+        self.losses, self.mses, self.num_pis, self.num_svs = [], [], [], []
+        self.qlosses, self.qmses = [], []
+        self.losses_history, self.mses_history = [], []
+        self.best_loss, self.best_mse = None, []
+        self.best_qloss, self.best_qmse = None, []
+        self.iter = iter_offset
+        self.valid = self.qvalid = False
+
+    # -- engine ---------------------------------------------------------------------------------
+    def _start_engine(self, engine_factory, device):
+        """The first engine (no optimizer yet); returns its device."""
+        self._engine_factory, self._device = engine_factory, device
+        self._engine = self._engine_key = None
+        self.optimizer1 = self.optimizer2 = self.optimizer3 = None
+        self.grad_clip_value_abs = None
+        self._make_engine(0.0, 0.0)
+        return self._engine.device
+
+    def _make_engine(self, pis_l1: float, u_l1: float):
+        """(Re-)create the engine when its configuration changed; ``_config`` adds the mode's shapes to the common
+        keywords, ``_engine_created`` hands a fresh engine what it has to know beyond the configuration."""
+        o1, o2, o3 = self.optimizer1, self.optimizer2, self.optimizer3
+        cfg = self._config(
+            channels=self.channels, kernels=self._kp, precision=self.precision, margin=self.margin,
+            use_determinant=bool(self.use_determinant), use_yuv=bool(self.use_yuv), train_pis=bool(self.train_pis),
+            train_gammas=bool(self.train_gammas), train_musx=bool(self.train_musx),
+            lr_expert=o1._lr if o1 else 0.0, lr_pis=o2._lr if o2 else 0.0, lr_steer=o3._lr if o3 else 0.0,
+            beta1=o1._beta1 if o1 else 0.9, beta2=o1._beta2 if o1 else 0.999, adam_eps=o1._epsilon if o1 else 1e-8,
+            grad_clip=float(self.grad_clip_value_abs or 0.0), pis_l1=float(pis_l1), u_l1=float(u_l1),
+            start_pis=self.kernels, only_y_gamma=bool(self.only_y_gamma), ssim_opt=bool(self.ssim_opt),
+            quantization_mode=int(self.quantization_mode), quantize_pis=bool(self.quantize_pis),
+            bit_depths=tuple(self.bit_depths), lower_bounds=tuple(self.lower_bounds),
+            upper_bounds=tuple(self.upper_bounds), train_inverse_cov=bool(self.train_inverse_cov),
+            radial_as=bool(self.radial_as), kernel_count_as_norm_l1=self.kernel_count_as_norm_l1)
+        key = repr(sorted(cfg.__dict__.items()))
+        if key != self._engine_key:
+            if self._engine is not None:
+                self._engine.close()
+            self._engine = self._engine_factory(cfg, self._device)
+            self._engine_key = key
+            self._engine_created()
+
+    def _hand_over_center_grid(self):
+        """use_diff_center with quantization_mode 2 / 3: the graph quantises the OFFSETS (smoe.py:746-747), so the engine
+        needs the kernel grid its ``musX`` (= grid + offset) is relative to."""
+        if self._mus_grid is None or int(self.quantization_mode) < 2:
+            return
+        self._mus_grid_dev = torch.from_numpy(np.ascontiguousarray(self._mus_grid, dtype=np.float32)).to(self._engine.device)
+        self._engine.set_center_grid(self._mus_grid_dev)
+
+    # -- optimizer (smoe.py:1079-1204) ----------------------------------------------------
+    def set_optimizer(self, optimizer1, optimizer2=None, optimizer3=None, optimizer4=None, optimizer5=None,
+                      grad_clip_value_abs=None):
+        self.optimizer1 = optimizer1
+        self.optimizer2 = optimizer1 if optimizer2 is None else optimizer2
+        self.optimizer3 = optimizer1 if optimizer3 is None else optimizer3
+        self.grad_clip_value_abs = grad_clip_value_abs
+        # a fresh set of optimizers means fresh slots and beta powers, as in TF
+        self._make_engine(0.0, 0.0)
+        self._state = self._engine.new_adam_state(self._params)
+
+    def _begin_train(self, val_iter, ukl_iter, optimizer1, optimizer2, optimizer3, grad_clip_value_abs):
+        """The head of ``train`` (smoe.py:1485-1497); returns ``ukl_iter``."""
+        if optimizer1:
+            self.set_optimizer(optimizer1, optimizer2, optimizer3, grad_clip_value_abs=grad_clip_value_abs)
+        assert self.optimizer1 is not None, "no optimizer found, you have to specify one!"
+        return val_iter if ukl_iter is None else ukl_iter
+
+    def _count_pis(self) -> torch.Tensor:
+        """num_pi_op of the local parameters: it counts pis_mask = qpis > 0 (smoe.py:480,1012)."""
+        pis = self._params["pis"]
+        if self.quantize_pis:
+            pis = _fake_quant_fixed(pis, self.lower_bounds[3], self.upper_bounds[3], self.bit_depths[3])
+        return (pis > 0).sum()
+
+    def _quantized_params(self) -> Dict[str, torch.Tensor]:
+        """``rparams`` on the device, as the engine takes parameters (smoe.py:1688-1689)."""
+        assert self.rparams is not None, "quantize_params + rescaler first (smoe.py:1499-1501)"
+        return {k: torch.from_numpy(v).to(self._engine.device) for k, v in self._local_rparams().items()}
+
+    # -- decoding on another grid -------------------------------------------------------------
+    def _render(self, scale, samples_per_block, dtype, quantized, want_argmax, to_host, use_lists=True):
+        """``render`` of both modes.  Hooks: ``_local_rparams``, ``_render_lists(quantized)``, ``_render_grid(m)`` ->
+        (tile grid, output extent, one sample table per axis), ``_engine_render`` and, with ``_block_local_ids``,
+        ``_global_ids``."""
+        d, n = self.dim_domain, self.batch_size_valued
+        if scale is not None and samples_per_block is not None:
+            raise ValueError("render: give scale or samples_per_block, not both")
+        if samples_per_block is not None:
+            spb = list(np.atleast_1d(samples_per_block))
+            spb = spb * d if len(spb) == 1 else spb
+            if len(spb) != d:
+                raise ValueError(f"render: samples_per_block needs one value or {d}")
+            m = [int(v) for v in spb]
+        else:
+            sc = list(np.atleast_1d(1 if scale is None else scale))
+            sc = sc * d if len(sc) == 1 else sc
+            if len(sc) != d:
+                raise ValueError(f"render: scale needs one value or {d}")
+            m = [max(1, int(round(float(v) * nl))) for v, nl in zip(sc, n)]
+        if min(m) < 1:
+            raise ValueError(f"render: at least one sample per {self._unit} and axis")
+        npdt = np.dtype(dtype)
+        if npdt not in (np.dtype(np.float32), np.dtype(np.uint8)):
+            raise ValueError("render: dtype must be float32 or uint8")
+        tdt = torch.uint8 if npdt == np.dtype(np.uint8) else torch.float32
+        eng = self._engine
+        if not hasattr(eng, "render"):
+            raise NotImplementedError("this engine has no render()")
+        dev, multi = eng.device, self.world_size > 1
+        params = self._quantized_params() if quantized else self._params
+        lists = self._render_lists(quantized) if use_lists else None
+        grid, extent, axes = self._render_grid(m)
+        axes = [torch.from_numpy(a).to(dev) for a in axes]
+        out = torch.zeros(tuple(extent) + (self.channels,), dtype=tdt, device=dev) if multi else None
+        res = self._engine_render(params, lists, axes, m, grid, extent, out, tdt, want_argmax)
+        img, ids = res if want_argmax else (res, None)
+        if ids is not None:
+            ids = ids.to(torch.int64)
+            if multi or self._block_local_ids:
+                # the tile index of every position, and whether the tile is one of this rank's
+                pos = [torch.arange(extent[l], device=dev) // m[l] for l in range(d)]
+                bid = pos[0]
+                for l in range(1, d):
+                    bid = bid.reshape(bid.shape + (1,)) * grid[l] + pos[l]
+                own = (bid >= self.lo) & (bid < self.hi)
+                if self._block_local_ids:
+                    ids = self._global_ids(ids, bid, own)
+                if multi:
+                    ids = torch.where(own, ids + 1, torch.zeros_like(ids))
+        if multi:
+            # the positions of other ranks' tiles are zero here: the sum over ranks is the image (ids shifted by one)
+            img = sdist.allreduce_sum_(img if tdt == torch.float32 else img.to(torch.int32)).to(tdt)
+            if ids is not None:
+                ids = sdist.allreduce_sum_(ids) - 1
+        if to_host:
+            img = img.cpu().numpy()
+            ids = None if ids is None else ids.cpu().numpy()
+        return (img, ids) if want_argmax else img
+
+    # -- getters (smoe.py:1795-1888) ------------------------------------------------------------
+    def get_reconstruction(self):
+        if not self.valid:
+            self.run_batched(train=False, update_reconstruction=True)
+        return self.reconstruction_image
+
+    def get_qreconstruction(self):
+        if not self.qvalid:
+            self.run_batched(train=False, update_reconstruction=True, with_quantized_params=True)
+        return self.qreconstruction_image
+
+    def get_weight_matrix_argmax(self):
+        if not self.valid:
+            self.run_batched(train=False, update_reconstruction=True)
+        return self.weight_matrix_argmax
+
+    def get_psnr(self) -> float:
+        """PSNR of the current reconstruction over the valid pixels (plotter.py:14-15)."""
+        rec = self.get_reconstruction()
+        mse = float(np.mean((rec.astype(np.float64) - self.image.astype(np.float64)) ** 2))
+        return float(-10.0 * np.log10(mse))
+
+    def get_qlosses(self):
+        return self.qlosses
+
+    def get_qmses(self):
+        return self.qmses
+
+    def get_losses(self):
+        return self.losses
+
+    def get_mses(self):
+        return self.mses
+
+    def get_num_pis(self):
+        return self.num_pis
+
+    def get_num_svs(self):
+        return self.num_svs
+
+    def get_best_loss(self):
+        return self.best_loss
+
+    def get_best_mse(self):
+        return self.best_mse
+
+    def get_losses_history(self):
+        return self.losses_history
+
+    def get_mses_history(self):
+        return self.mses_history
+
+    def get_iter(self):
+        return self.iter
+
+    def get_original_image(self):
+        return np.squeeze(self.image)
+
+
+class Smoe(_SmoeBase):
+    _unit, _block_local_ids = "block", True
+
     def __init__(self, image, kernels_per_dim=None, train_pis=True, init_params=None, start_batches=1,
                  batch_size=None, train_gammas=True, train_musx=True, use_diff_center=False, radial_as=False,
                  use_determinant=False, normalize_pis=True, quantization_mode=0, bit_depths=None,
@@ -187,8 +428,7 @@ class Smoe:
         for name, val in unsupported.items():
             if val:
                 raise NotImplementedError(f"Smoe({name}=True) is outside the per-block hot path (SURVEY section 8)")
-        if quantization_mode not in (0, 1, 2, 3):
-            raise ValueError("quantization_mode must be 0, 1, 2 or 3")                # smoe_test.py:298-301
+        self._set_quantizer(quantization_mode, quantize_pis, bit_depths, lower_bounds, upper_bounds)
         if add_kernel_slots:
             raise NotImplementedError("progressive kernel adding changes K over time; not part of the hot path")
         if overlap_of_batches:
@@ -198,29 +438,16 @@ class Smoe:
         assert kernels_per_dim is not None or init_params is not None, \
             "You need to specify the kernel grid size or give initial parameters."   # smoe.py:249-250
 
-        image = np.asarray(image, dtype=np.float32)
-        self.image = image
-        self.dim_domain = image.ndim - 1                                # smoe.py:227
-        self.num_pixel = int(np.prod(image.shape[:self.dim_domain]))    # smoe.py:228
-        self.precision = precision
-        self.use_yuv = bool(use_yuv) and image.shape[-1] == 3           # smoe_test.py:41-44
-        self.only_y_gamma = bool(only_y_gamma) and self.use_yuv         # smoe_test.py:43-44
+        image = self._set_image(image, precision, margin, use_yuv, only_y_gamma)
         self.ssim_opt = ssim_opt
         self.use_diff_center = use_diff_center
         self.radial_as = radial_as
         self.kernel_count_as_norm_l1 = bool(kernel_count_as_norm_l1)
         self.use_determinant = use_determinant
-        self.quantization_mode = quantization_mode
-        self.quantize_pis = bool(quantize_pis) or quantization_mode >= 2               # smoe_test.py:36-37, smoe.py:474
-        # bit depths / bounds in the order A, musX, nu_e, pis, gamma_e; None -> the CLI defaults (smoe_test.py:302-309)
-        self.bit_depths = [20, 18, 6, 10, 10] if bit_depths is None else list(bit_depths)
-        self.lower_bounds = [-2500, -.3, -5, 0, -32] if lower_bounds is None else list(lower_bounds)
-        self.upper_bounds = [2500, 1.3, 5, 2, 32] if upper_bounds is None else list(upper_bounds)
         self.train_pis, self.train_gammas, self.train_musx = train_pis, train_gammas, train_musx
         self.train_inverse_cov = train_inverse_cov
         self.train_trafo = train_trafo
         self.affines = affines
-        self.margin = margin
         self.overlap = overlap_of_batches
         self.add_kernel_slots = 0
         self.loss_mask = loss_mask
@@ -229,15 +456,7 @@ class Smoe:
 
         # -- block shape (smoe.py:231-247) -----------------------------------------------
         d = self.dim_domain
-        if batch_size is None or batch_size[0] is None:
-            # smoe.py:229,243: block shape from the desired number of batches (1 -> the whole image)
-            bs = blk.get_batch_shape(start_batches, tuple(image.shape[:d]) + (d + image.shape[-1],))[:-1]
-        elif len(batch_size) == d:
-            bs = tuple(int(b) for b in batch_size)
-        elif len(batch_size) == 1:
-            bs = tuple(int(batch_size[0]) for _ in range(d))
-        else:
-            raise ValueError("Required BatchSize doesn't fit to input dimension")    # smoe.py:237
+        bs = self._batch_shape(batch_size, start_batches)
         self.batch_size_valued = bs
         self.batch_size = bs
         self.grid = blk.grid_shape(image.shape[:d], bs)
@@ -262,8 +481,7 @@ class Smoe:
         self.B = blocks_local.shape[0]
         N = int(np.prod(bs))
         self.N = N
-        C = image.shape[-1]
-        self.channels = C
+        C = self.channels
 
         # -- initial parameters (smoe.py:252-262) ----------------------------------------
         if init_params:
@@ -309,14 +527,7 @@ class Smoe:
         self.kernel_count = K * self.num_blocks
 
         # -- device state ---------------------------------------------------------------
-        self._engine_factory = engine_factory or _default_engine_factory
-        self._device = device
-        self._engine = None
-        self._engine_key = None
-        self.optimizer1 = self.optimizer2 = self.optimizer3 = None
-        self.grad_clip_value_abs = None
-        self._make_engine(pis_l1=0.0, u_l1=0.0)
-        dev = self._engine.device
+        dev = self._start_engine(engine_factory or _default_engine_factory, device)
         self._target = torch.from_numpy(blk.to_planar(blocks_local)).to(dev)
         lw = None
         if self.padded:
@@ -339,56 +550,19 @@ class Smoe:
         # them by the error-proportional ones (smoe.py:270-272,906-907,1768-1769)
         self._sampl_prob = torch.full((self.B, N), 1.0 / N, dtype=torch.float32, device=dev)
 
-        # -- histories (smoe.py:183-199) -------------------------------------------------
-        self.losses, self.mses, self.num_pis, self.num_svs = [], [], [], []
-        self.qlosses, self.qmses = [], []
-        self.losses_history, self.mses_history = [], []
-        self.best_loss = None
-        self.best_mse = []
-        self.iter = iter_offset
-        self.valid = False
+        self._reset_histories(iter_offset)
         self._images = None                  # reconstruction_image / weight_matrix_argmax / weight_matrix (lazy, see _stitch)
-        self.qvalid = False
         self._qimages = None                 # their with_quantized_params counterparts
-        self.best_qloss = None
-        self.best_qmse = []
 
     # ------------------------------------------------------------------------------------
-    def _make_engine(self, pis_l1: float, u_l1: float):
-        o1, o2, o3 = self.optimizer1, self.optimizer2, self.optimizer3
-        cfg = EngineConfig(
-            block_shape=self.batch_size_valued, channels=self.image.shape[-1], kernels=self._kp,
-            precision=self.precision, margin=self.margin, use_determinant=bool(self.use_determinant),
-            use_yuv=bool(self.use_yuv), train_pis=bool(self.train_pis), train_gammas=bool(self.train_gammas),
-            train_musx=bool(self.train_musx),
-            lr_expert=o1._lr if o1 else 0.0, lr_pis=o2._lr if o2 else 0.0, lr_steer=o3._lr if o3 else 0.0,
-            beta1=o1._beta1 if o1 else 0.9, beta2=o1._beta2 if o1 else 0.999,
-            adam_eps=o1._epsilon if o1 else 1e-8,
-            grad_clip=float(self.grad_clip_value_abs or 0.0), pis_l1=float(pis_l1), u_l1=float(u_l1),
-            start_pis=self.kernels, only_y_gamma=bool(self.only_y_gamma), ssim_opt=bool(self.ssim_opt),
-            quantization_mode=int(self.quantization_mode), quantize_pis=bool(self.quantize_pis),
-            bit_depths=tuple(self.bit_depths), lower_bounds=tuple(self.lower_bounds),
-            upper_bounds=tuple(self.upper_bounds), train_inverse_cov=bool(self.train_inverse_cov),
-            radial_as=bool(self.radial_as), kernel_count_as_norm_l1=self.kernel_count_as_norm_l1)
-        key = tuple(sorted(cfg.__dict__.items(), key=lambda kv: kv[0]))
-        key = repr(key)
-        if key != self._engine_key:
-            if self._engine is not None:
-                self._engine.close()
-            self._engine = self._engine_factory(cfg, self._device)
-            self._engine_key = key
-            # the kernels (= the summation order inside a block) are chosen for the whole image, not for this rank's shard
-            if hasattr(self._engine, "set_total_blocks"):
-                self._engine.set_total_blocks(self.num_blocks)
-            self._hand_over_center_grid()
+    def _config(self, **common):
+        return EngineConfig(block_shape=self.batch_size_valued, **common)
 
-    def _hand_over_center_grid(self):
-        """use_diff_center with quantization_mode 2 / 3: the graph quantises the OFFSETS (smoe.py:746-747), so the engine
-        needs the kernel grid its ``musX`` (= grid + offset) is relative to."""
-        if getattr(self, "_mus_grid", None) is None or int(self.quantization_mode) < 2:
-            return
-        self._mus_grid_dev = torch.from_numpy(np.ascontiguousarray(self._mus_grid, dtype=np.float32)).to(self._engine.device)
-        self._engine.set_center_grid(self._mus_grid_dev)
+    def _engine_created(self):
+        # the kernels (= the summation order inside a block) are chosen for the whole image, not for this rank's shard
+        if hasattr(self._engine, "set_total_blocks"):
+            self._engine.set_total_blocks(self.num_blocks)
+        self._hand_over_center_grid()
 
     @property
     def kernel_list_per_batch(self) -> List[np.ndarray]:
@@ -398,25 +572,10 @@ class Smoe:
         mask = ((bits[:, None] >> np.arange(K, dtype=np.uint32)[None, :]) & 1).astype(bool)
         return [m for m in mask]
 
-    # -- optimizer (smoe.py:1079-1204) ----------------------------------------------------
-    def set_optimizer(self, optimizer1, optimizer2=None, optimizer3=None, optimizer4=None, optimizer5=None,
-                      grad_clip_value_abs=None):
-        self.optimizer1 = optimizer1
-        self.optimizer2 = optimizer1 if optimizer2 is None else optimizer2
-        self.optimizer3 = optimizer1 if optimizer3 is None else optimizer3
-        self.grad_clip_value_abs = grad_clip_value_abs
-        # a fresh set of optimizers means fresh slots and beta powers, as in TF
-        self._make_engine(0.0, 0.0)
-        self._state = self._engine.new_adam_state(self._params)
-
     # -- passes ----------------------------------------------------------------------------
     def _global(self, loss, sse, valid_only=False):
         s = self._engine.reduce_scalars(loss, sse, None)
-        pis = self._params["pis"]
-        if self.quantize_pis:                                        # num_pi_op counts pis_mask = qpis > 0 (smoe.py:480,1012)
-            pis = _fake_quant_fixed(pis, self.lower_bounds[3], self.upper_bounds[3], self.bit_depths[3])
-        npi = (pis > 0).sum().to(torch.float64)
-        s[2] = npi
+        s[2] = self._count_pis().to(torch.float64)       # of this rank's blocks: the parameters are sharded
         sdist.allreduce_sum_(s)
         s = s.cpu().numpy()
         total_px = float(self.num_blocks) * self.N
@@ -442,11 +601,8 @@ class Smoe:
         if with_quantized_params:
             # smoe.py:1688-1689: the rescaled parameters are fed over the masked-parameter tensors;
             # the kernel lists are not touched (smoe.py:1763)
-            assert self.rparams is not None, "quantize_params + rescaler first (smoe.py:1499-1501)"
+            rp = self._quantized_params()
             self.qvalid = False
-            dev = eng.device
-            rp = {k: np.ascontiguousarray(self.rparams[k][self.lo:self.hi], dtype=np.float32) for k in PARAM_NAMES}
-            rp = {k: torch.from_numpy(v).to(dev) for k, v in _pad_kernels(rp, self._kp).items()}
             out = eng.forward(self._target, rp, self._active, loss_w=self._loss_w,
                               want_recon=update_reconstruction, want_argmax=update_reconstruction,
                               want_gate=update_reconstruction, update_active=False)
@@ -563,11 +719,7 @@ class Smoe:
     def train(self, num_iter, val_iter=100, ukl_iter=None, optimizer1=None, optimizer2=None, optimizer3=None,
               grad_clip_value_abs=None, pis_l1=0, u_l1=0, sv_l1_sub_l2=0, sampling_percentage=100,
               callbacks=(), with_inc=False, train_inc=False, train_orig=True, use_loss_mask=False):
-        if ukl_iter is None:
-            ukl_iter = val_iter
-        if optimizer1:
-            self.set_optimizer(optimizer1, optimizer2, optimizer3, grad_clip_value_abs=grad_clip_value_abs)
-        assert self.optimizer1 is not None, "no optimizer found, you have to specify one!"
+        ukl_iter = self._begin_train(val_iter, ukl_iter, optimizer1, optimizer2, optimizer3, grad_clip_value_abs)
         if with_inc or train_inc or not train_orig:
             raise NotImplementedError("kernel-adding options are outside the hot path")
         self._train_sampling = sampling_percentage if (sampling_percentage < 100 and not self.ssim_opt) else None
@@ -621,16 +773,6 @@ class Smoe:
     def get_best_params(self):
         return self._gather_params(self._best)
 
-    def get_reconstruction(self):
-        if not self.valid:
-            self.run_batched(train=False, update_reconstruction=True)
-        return self.reconstruction_image
-
-    def get_qreconstruction(self):
-        if not self.qvalid:
-            self.run_batched(train=False, update_reconstruction=True, with_quantized_params=True)
-        return self.qreconstruction_image
-
     def render(self, scale=None, samples_per_block=None, dtype=np.float32, quantized=False, want_argmax=False,
                to_host=True):
         """Decode the fitted blocks on another sampling grid, on the device (the engine's ``render``): every block is a
@@ -645,123 +787,37 @@ class Smoe:
         ``get_weight_matrix_argmax``; -1 where no kernel has influence on the sample).  ``to_host=False`` returns device
         tensors.  Several ranks: every rank renders its blocks and the images are summed; the result is the same on
         every rank and for every number of ranks."""
-        d, n = self.dim_domain, self.batch_size_valued
-        if scale is not None and samples_per_block is not None:
-            raise ValueError("render: give scale or samples_per_block, not both")
-        if samples_per_block is not None:
-            spb = list(np.atleast_1d(samples_per_block))
-            spb = spb * d if len(spb) == 1 else spb
-            if len(spb) != d:
-                raise ValueError(f"render: samples_per_block needs one value or {d}")
-            m = [int(v) for v in spb]
-        else:
-            sc = list(np.atleast_1d(1 if scale is None else scale))
-            sc = sc * d if len(sc) == 1 else sc
-            if len(sc) != d:
-                raise ValueError(f"render: scale needs one value or {d}")
-            m = [max(1, int(round(float(v) * nl))) for v, nl in zip(sc, n)]
-        if min(m) < 1:
-            raise ValueError("render: at least one sample per block and axis")
-        extent = [max(1, int(self.image.shape[l]) * m[l] // n[l]) for l in range(d)]
-        npdt = np.dtype(dtype)
-        if npdt not in (np.dtype(np.float32), np.dtype(np.uint8)):
-            raise ValueError("render: dtype must be float32 or uint8")
-        tdt = torch.uint8 if npdt == np.dtype(np.uint8) else torch.float32
-        eng = self._engine
-        if not hasattr(eng, "render"):
-            raise NotImplementedError("this engine has no render()")
-        dev = eng.device
-        if quantized:
-            assert self.rparams is not None, "quantize_params + rescaler first (smoe.py:1499-1501)"
-            rp = {k: np.ascontiguousarray(self.rparams[k][self.lo:self.hi], dtype=np.float32) for k in PARAM_NAMES}
-            params = {k: torch.from_numpy(v).to(dev) for k, v in _pad_kernels(rp, self._kp).items()}
-        else:
-            params = self._params
-        axes = [torch.from_numpy(blk.render_axis(n[l], m[l])).to(dev) for l in range(d)]
-        out = None
-        if self.world_size > 1:
-            out = torch.zeros(tuple(extent) + (self.channels,), dtype=tdt, device=dev)
+        return self._render(scale, samples_per_block, dtype, quantized, want_argmax, to_host)
+
+    # hooks of _render
+    def _local_rparams(self):
+        rp = {k: np.ascontiguousarray(self.rparams[k][self.lo:self.hi], dtype=np.float32) for k in PARAM_NAMES}
+        return _pad_kernels(rp, self._kp)
+
+    def _render_lists(self, quantized):
         # the kernel lists of the pass behind get_reconstruction() while that reconstruction is current (the pass prunes
         # its lists only after it has evaluated with them), the current lists otherwise
-        active = self._active
         if self.valid and not quantized and getattr(self, "_recon_active", None) is not None:
-            active = self._recon_active
-        res = eng.render(params, active, axes, self.grid, extent, first_block=self.lo, out=out, dtype=tdt,
-                         want_argmax=want_argmax)
-        img, am = res if want_argmax else (res, None)
-        ids = None
-        if want_argmax:
-            # global kernel id = block index * K + kernel (as _assemble_one forms it); the block index of every position
-            pos = [torch.arange(extent[l], device=dev) // m[l] for l in range(d)]
-            bid = pos[0]
-            for l in range(1, d):
-                bid = bid.reshape(bid.shape + (1,)) * self.grid[l] + pos[l]
-            own = (bid >= self.lo) & (bid < self.hi)
-            am = am.to(torch.int64)
-            ids = torch.where(own & (am != 255), am + bid * self.kernels, torch.full_like(am, -1))
-            if self.world_size > 1:
-                ids = torch.where(own, ids + 1, torch.zeros_like(ids))
-        if self.world_size > 1:
-            # the positions of other ranks' blocks are zero here: the sum over ranks is the image
-            img = sdist.allreduce_sum_(img if tdt == torch.float32 else img.to(torch.int32)).to(tdt)
-            if ids is not None:
-                ids = sdist.allreduce_sum_(ids) - 1
-        if to_host:
-            img = img.cpu().numpy()
-            ids = None if ids is None else ids.cpu().numpy()
-        return (img, ids) if want_argmax else img
+            return self._recon_active
+        return self._active
 
-    def get_qlosses(self):
-        return self.qlosses
+    def _render_grid(self, m):
+        n = self.batch_size_valued
+        extent = [max(1, int(self.image.shape[l]) * m[l] // n[l]) for l in range(self.dim_domain)]   # crops ragged padding
+        return self.grid, extent, [blk.render_axis(n[l], m[l]) for l in range(self.dim_domain)]
 
-    def get_qmses(self):
-        return self.qmses
+    def _engine_render(self, params, active, axes, m, grid, extent, out, tdt, want_argmax):
+        return self._engine.render(params, active, axes, grid, extent, first_block=self.lo, out=out, dtype=tdt,
+                                   want_argmax=want_argmax)
 
-    def get_weight_matrix_argmax(self):
-        if not self.valid:
-            self.run_batched(train=False, update_reconstruction=True)
-        return self.weight_matrix_argmax
+    def _global_ids(self, am, bid, own):
+        # global kernel id = block index * K + kernel (as _assemble_one forms it); -1: none, or another rank's block
+        return torch.where(own & (am != 255), am + bid * self.kernels, torch.full_like(am, -1))
 
     def get_weight_matrix(self):
         if not self.valid:
             self.run_batched(train=False, update_reconstruction=True)
         return self.weight_matrix
-
-    def get_psnr(self) -> float:
-        """PSNR of the current reconstruction over the valid pixels (plotter.py:14-15)."""
-        rec = self.get_reconstruction()
-        mse = float(np.mean((rec.astype(np.float64) - self.image.astype(np.float64)) ** 2))
-        return float(-10.0 * np.log10(mse))
-
-    def get_losses(self):
-        return self.losses
-
-    def get_mses(self):
-        return self.mses
-
-    def get_num_pis(self):
-        return self.num_pis
-
-    def get_num_svs(self):
-        return self.num_svs
-
-    def get_best_loss(self):
-        return self.best_loss
-
-    def get_best_mse(self):
-        return self.best_mse
-
-    def get_losses_history(self):
-        return self.losses_history
-
-    def get_mses_history(self):
-        return self.mses_history
-
-    def get_iter(self):
-        return self.iter
-
-    def get_original_image(self):
-        return np.squeeze(self.image)
 
     # -- checkpoint / restore (replaces the tf.train.Saver of smoe.py:1066-1077) ---------------
     def checkpoint(self, path):
@@ -812,7 +868,7 @@ def _default_shared_factory(cfg, device):
     return SharedEngine(cfg, device)
 
 
-class SharedSmoe:
+class SharedSmoe(_SmoeBase):
     """``Smoe`` with ONE global kernel set, as the reference fits whole images
     (``Smoe(image, kernels_per_dim=[12, 12], batch_size=[32, 32])``): ``kernels_per_dim`` is the
     global kernel grid, ``batch_size`` the pixel batch of a pass (smoe.py:231-247), every batch keeps
@@ -822,6 +878,7 @@ class SharedSmoe:
     ranks and the accumulated gradient buffer is all-reduced (RCCL) before the Adam step.
     ``overlap_of_batches`` > 0: the halo of every batch takes part in the kernel-list influence test
     only (its loss is cropped, smoe.py:909-923)."""
+    _unit = "batch"
 
     def __init__(self, image, kernels_per_dim=None, train_pis=True, init_params=None, start_batches=1,
                  batch_size=None, train_gammas=True, train_musx=True, use_determinant=False, normalize_pis=True,
@@ -832,38 +889,20 @@ class SharedSmoe:
         for name, val in unsupported.items():
             if val:
                 raise NotImplementedError(f"SharedSmoe({name}=...) is outside the hot path (SURVEY section 8)")
-        if quantization_mode not in (0, 1, 2, 3):
-            raise ValueError("quantization_mode must be 0, 1, 2 or 3")                # smoe_test.py:298-301
+        self._set_quantizer(quantization_mode, quantize_pis, bit_depths, lower_bounds, upper_bounds)
         self.kernel_count_as_norm_l1 = bool(kernel_count_as_norm_l1)                  # smoe.py:1022-1027
         assert kernels_per_dim is not None or init_params is not None, \
             "You need to specify the kernel grid size or give initial parameters."
-        image = np.asarray(image, dtype=np.float32)
-        self.image = image
-        d = self.dim_domain = image.ndim - 1
-        self.num_pixel = int(np.prod(image.shape[:d]))
-        self.precision, self.margin = precision, margin
-        self.use_yuv = bool(use_yuv) and image.shape[-1] == 3
+        image = self._set_image(image, precision, margin, use_yuv, only_y_gamma)
+        d = self.dim_domain
         self.use_determinant = use_determinant
         self.train_pis, self.train_gammas, self.train_musx = train_pis, train_gammas, train_musx
-        self.quantization_mode = int(quantization_mode)
-        self.quantize_pis = bool(quantize_pis) or quantization_mode >= 2           # smoe.py:474, smoe_test.py:36-37
-        self.bit_depths = [20, 18, 6, 10, 10] if bit_depths is None else list(bit_depths)
-        self.lower_bounds = [-2500, -.3, -5, 0, -32] if lower_bounds is None else list(lower_bounds)
-        self.upper_bounds = [2500, 1.3, 5, 2, 32] if upper_bounds is None else list(upper_bounds)
         self.radial_as = bool(radial_as)                                   # smoe.py:429-434,714-719
         self.train_inverse_cov = bool(train_inverse_cov)                  # smoe.py:41: the constructor default is True
         self.ssim_opt = bool(ssim_opt)                                    # smoe.py:929,980-1011: 1 - SSIM per batch
-        self.only_y_gamma = bool(only_y_gamma) and self.use_yuv          # smoe_test.py:43-44, smoe.py:725-729
         self.use_diff_center = bool(use_diff_center)
         self.overlap = int(overlap_of_batches)                            # smoe.py:244
-        if batch_size is None or batch_size[0] is None:
-            bs = blk.get_batch_shape(start_batches, tuple(image.shape[:d]) + (d + image.shape[-1],))[:-1]
-        elif len(batch_size) == d:
-            bs = tuple(int(b) for b in batch_size)
-        elif len(batch_size) == 1:
-            bs = tuple(int(batch_size[0]) for _ in range(d))
-        else:
-            raise ValueError("Required BatchSize doesn't fit to input dimension")
+        bs = self._batch_shape(batch_size, start_batches)
         for ii in range(d):                                               # smoe.py:239-241
             if image.shape[ii] % bs[ii] > 0:
                 raise ValueError("Required BatchSize is not compatible to input dimensions")
@@ -886,17 +925,11 @@ class SharedSmoe:
         if self.radial_as:                    # one steering value per kernel: A_init[:, 0, 0] tiled over the diagonal
             a0 = p0["A_diagonal"] if p0["A_diagonal"].ndim == 1 else p0["A_diagonal"][:, 0, 0]
             p0["A_diagonal"] = np.ascontiguousarray(a0[:, None, None] * np.eye(d, dtype=np.float32))
-        self.kernels = self.start_pis = self.kernel_count = p0["pis"].shape[0]
+        self.kernels = self._kp = self.start_pis = self.kernel_count = p0["pis"].shape[0]      # no padding kernels here
         # use_diff_center (smoe.py:390-394,746-747): the trained variable is the offset from the kernel grid; the
         # engine works on grid + offset, the getters subtract the grid
         self._mus_grid = np.ascontiguousarray(p0["musX"]).copy() if self.use_diff_center else None
-        self._factory = engine_factory or _default_shared_factory
-        self._device = device
-        self._engine, self._engine_key = None, None
-        self.optimizer1 = self.optimizer2 = self.optimizer3 = None
-        self.grad_clip_value_abs = None
-        self._make_engine(0.0, 0.0)
-        dev = self._engine.device
+        dev = self._start_engine(engine_factory or _default_shared_factory, device)
         self._target = torch.from_numpy(blk.to_planar(blocks_all[self.lo:self.hi])).to(dev)
         self._params = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in p0.items()}
         self._best = {k: v.clone() for k, v in self._params.items()}
@@ -911,46 +944,19 @@ class SharedSmoe:
             lm, _ = blk.image_to_blocks(np.asarray(loss_mask, dtype=np.float32)[..., None], bs)
             self._loss_w = torch.from_numpy(np.ascontiguousarray(lm.reshape(self.num_batches, -1))).to(dev)
             self._engine.set_loss_weights(self._loss_w)
-        self.losses, self.mses, self.num_pis, self.num_svs = [], [], [], []
-        self.losses_history, self.mses_history = [], []
-        self.best_loss, self.best_mse = None, []
-        self.iter = iter_offset
-        self.valid = False
+        self._reset_histories(iter_offset)
         self._recon_lists = self._qrecon_lists = None
-        self.reconstruction_image = self.weight_matrix_argmax = None
+        self.reconstruction_image = self.weight_matrix_argmax = self.qreconstruction_image = None
         self.qparams = self.rparams = None                                # quantizer.py products (leading axis 1 = the model)
-        self.qreconstruction_image = None
-        self.qvalid = False
-        self.qlosses, self.qmses = [], []
-        self.best_qloss, self.best_qmse = None, []
 
-    def _make_engine(self, pis_l1, u_l1):
-        from .engine import SharedConfig
-        o1, o2, o3 = self.optimizer1, self.optimizer2, self.optimizer3
-        cfg = SharedConfig(
-            image_shape=tuple(self.image.shape[:self.dim_domain]), batch_shape=self.batch_size_valued,
-            channels=self.image.shape[-1], kernels=self.kernels, precision=self.precision, margin=self.margin,
-            use_determinant=bool(self.use_determinant), use_yuv=bool(self.use_yuv), train_pis=bool(self.train_pis),
-            train_gammas=bool(self.train_gammas), train_musx=bool(self.train_musx),
-            lr_expert=o1._lr if o1 else 0.0, lr_pis=o2._lr if o2 else 0.0, lr_steer=o3._lr if o3 else 0.0,
-            beta1=o1._beta1 if o1 else 0.9, beta2=o1._beta2 if o1 else 0.999, adam_eps=o1._epsilon if o1 else 1e-8,
-            grad_clip=float(self.grad_clip_value_abs or 0.0), pis_l1=float(pis_l1), u_l1=float(u_l1),
-            start_pis=self.kernels, overlap=self.overlap, quantization_mode=self.quantization_mode,
-            quantize_pis=self.quantize_pis, bit_depths=tuple(self.bit_depths), lower_bounds=tuple(self.lower_bounds),
-            upper_bounds=tuple(self.upper_bounds), only_y_gamma=self.only_y_gamma, ssim_opt=self.ssim_opt,
-            train_inverse_cov=self.train_inverse_cov, radial_as=self.radial_as,
-            kernel_count_as_norm_l1=self.kernel_count_as_norm_l1)
-        key = repr(sorted(cfg.__dict__.items()))
-        if key != self._engine_key:
-            if self._engine is not None:
-                self._engine.close()
-            self._engine = self._factory(cfg, self._device)
-            self._engine_key = key
-            if self._mus_grid is not None and self.quantization_mode >= 2:   # the graph quantises the OFFSETS (smoe.py:746-747)
-                self._mus_grid_dev = torch.from_numpy(np.ascontiguousarray(self._mus_grid, dtype=np.float32)).to(self._engine.device)
-                self._engine.set_center_grid(self._mus_grid_dev)
-            if getattr(self, "_loss_w", None) is not None:                # a re-created engine needs the weights again
-                self._engine.set_loss_weights(self._loss_w)
+    def _config(self, **common):
+        return SharedConfig(image_shape=tuple(self.image.shape[:self.dim_domain]), batch_shape=self.batch_size_valued,
+                            overlap=self.overlap, **common)
+
+    def _engine_created(self):
+        self._hand_over_center_grid()
+        if getattr(self, "_loss_w", None) is not None:                    # a re-created engine needs the weights again
+            self._engine.set_loss_weights(self._loss_w)
 
     @property
     def kernel_list_per_batch(self):
@@ -958,25 +964,13 @@ class SharedSmoe:
         K = self.kernels
         return [np.array([(row[k >> 5] >> (k & 31)) & 1 for k in range(K)], dtype=bool) for row in bits]
 
-    def set_optimizer(self, optimizer1, optimizer2=None, optimizer3=None, optimizer4=None, optimizer5=None,
-                      grad_clip_value_abs=None):
-        self.optimizer1 = optimizer1
-        self.optimizer2 = optimizer1 if optimizer2 is None else optimizer2
-        self.optimizer3 = optimizer1 if optimizer3 is None else optimizer3
-        self.grad_clip_value_abs = grad_clip_value_abs
-        self._make_engine(0.0, 0.0)
-        self._state = self._engine.new_adam_state(self._params)
-
     def _global(self, loss, sse):
         s = torch.stack([loss.double().sum(), sse.double().sum()])
         sdist.allreduce_sum_(s)
         s = s.cpu().numpy()
         loss_val = float(s[0]) * self.Nb / self.num_pixel                              # smoe.py:1758
-        mse_val = float(s[1]) / (self.num_pixel * self.image.shape[-1]) * (2 ** self.precision) ** 2
-        pis = self._params["pis"]
-        if self.quantize_pis:                                        # pis_mask = qpis > 0 (smoe.py:480,1012)
-            pis = _fake_quant_fixed(pis, self.lower_bounds[3], self.upper_bounds[3], self.bit_depths[3])
-        return loss_val, mse_val, int((pis > 0).sum().item())
+        mse_val = float(s[1]) / (self.num_pixel * self.channels) * (2 ** self.precision) ** 2
+        return loss_val, mse_val, int(self._count_pis().item())      # not reduced: the parameters are replicated
 
     def _quantize(self):
         """quantize_params + rescaler (quantizer.py:4-145) on the global kernel set (one model = leading axis 1)."""
@@ -994,9 +988,8 @@ class SharedSmoe:
         eng, nb = self._engine, self.hi - self.lo
         dev = eng.device
         if with_quantized_params:                                         # smoe.py:1688-1689: the lists are not touched
-            assert self.rparams is not None, "quantize_params + rescaler first (smoe.py:1499-1501)"
+            rp = self._quantized_params()
             self.qvalid = False
-            rp = {k: torch.from_numpy(np.ascontiguousarray(self.rparams[k][0], dtype=np.float32)).to(dev) for k in PARAM_NAMES}
             out = eng.forward(self._target, rp, self._lists, first_batch=self.lo, want_recon=update_reconstruction,
                               want_argmax=False, update_lists=False)
             if update_reconstruction:
@@ -1035,11 +1028,7 @@ class SharedSmoe:
 
     def train(self, num_iter, val_iter=100, ukl_iter=None, optimizer1=None, optimizer2=None, optimizer3=None,
               grad_clip_value_abs=None, pis_l1=0, u_l1=0, callbacks=(), **kw):
-        if ukl_iter is None:
-            ukl_iter = val_iter
-        if optimizer1:
-            self.set_optimizer(optimizer1, optimizer2, optimizer3, grad_clip_value_abs=grad_clip_value_abs)
-        assert self.optimizer1 is not None, "no optimizer found, you have to specify one!"
+        ukl_iter = self._begin_train(val_iter, ukl_iter, optimizer1, optimizer2, optimizer3, grad_clip_value_abs)
         self._make_engine(pis_l1, u_l1)
         _train_loop(self, num_iter, val_iter, ukl_iter, pis_l1, u_l1, callbacks)
 
@@ -1104,114 +1093,25 @@ class SharedSmoe:
         weight was zero, but its gate still sat in the normaliser of the pass that pruned it.)
         Several ranks: every rank renders its batches and the images are summed; the result is the same on every rank
         and for every number of ranks."""
-        d, n = self.dim_domain, self.batch_size_valued
-        if scale is not None and samples_per_block is not None:
-            raise ValueError("render: give scale or samples_per_block, not both")
-        if samples_per_block is not None:
-            spb = list(np.atleast_1d(samples_per_block))
-            spb = spb * d if len(spb) == 1 else spb
-            if len(spb) != d:
-                raise ValueError(f"render: samples_per_block needs one value or {d}")
-            m = [int(v) for v in spb]
-        else:
-            sc = list(np.atleast_1d(1 if scale is None else scale))
-            sc = sc * d if len(sc) == 1 else sc
-            if len(sc) != d:
-                raise ValueError(f"render: scale needs one value or {d}")
-            m = [max(1, int(round(float(v) * nl))) for v, nl in zip(sc, n)]
-        if min(m) < 1:
-            raise ValueError("render: at least one sample per batch and axis")
-        npdt = np.dtype(dtype)
-        if npdt not in (np.dtype(np.float32), np.dtype(np.uint8)):
-            raise ValueError("render: dtype must be float32 or uint8")
-        tdt = torch.uint8 if npdt == np.dtype(np.uint8) else torch.float32
-        eng = self._engine
-        if not hasattr(eng, "render"):
-            raise NotImplementedError("this engine has no render()")
-        dev = eng.device
-        grid = [int(self.image.shape[l]) // n[l] for l in range(d)]
-        extent = [grid[l] * m[l] for l in range(d)]
-        if quantized:
-            assert self.rparams is not None, "quantize_params + rescaler first (smoe.py:1499-1501)"
-            params = {k: torch.from_numpy(np.ascontiguousarray(self.rparams[k][0], dtype=np.float32)).to(dev) for k in PARAM_NAMES}
-        else:
-            params = self._params
-        axes = [torch.from_numpy(blk.render_axis(int(self.image.shape[l]), extent[l])).to(dev) for l in range(d)]
-        lists = None
-        if use_lists:
-            lists = self._lists
-            if quantized and self.qvalid and getattr(self, "_qrecon_lists", None) is not None:
-                lists = self._qrecon_lists
-            elif not quantized and self.valid and getattr(self, "_recon_lists", None) is not None:
-                lists = self._recon_lists
-        out = None
-        if self.world_size > 1:
-            out = torch.zeros(tuple(extent) + (self.image.shape[-1],), dtype=tdt, device=dev)
-        res = eng.render(params, lists, axes, m, first_batch=self.lo, out=out, dtype=tdt, want_argmax=want_argmax,
-                         num_batches=self.hi - self.lo)
-        img, ids = res if want_argmax else (res, None)
-        if ids is not None:
-            ids = ids.to(torch.int64)
-        if self.world_size > 1:
-            # the positions of other ranks' batches are zero here: the sum over ranks is the image (ids shifted by one)
-            img = sdist.allreduce_sum_(img if tdt == torch.float32 else img.to(torch.int32)).to(tdt)
-            if ids is not None:
-                pos = [torch.arange(extent[l], device=dev) // m[l] for l in range(d)]
-                bid = pos[0]
-                for l in range(1, d):
-                    bid = bid.reshape(bid.shape + (1,)) * grid[l] + pos[l]
-                own = (bid >= self.lo) & (bid < self.hi)
-                ids = sdist.allreduce_sum_(torch.where(own, ids + 1, torch.zeros_like(ids))) - 1
-        if to_host:
-            img = img.cpu().numpy()
-            ids = None if ids is None else ids.cpu().numpy()
-        return (img, ids) if want_argmax else img
+        return self._render(scale, samples_per_block, dtype, quantized, want_argmax, to_host, use_lists)
 
-    def get_reconstruction(self):
-        if not self.valid:
-            self.run_batched(train=False, update_reconstruction=True)
-        return self.reconstruction_image
+    # hooks of _render
+    def _local_rparams(self):
+        return {k: np.ascontiguousarray(self.rparams[k][0], dtype=np.float32) for k in PARAM_NAMES}
 
-    def get_weight_matrix_argmax(self):
-        if not self.valid:
-            self.run_batched(train=False, update_reconstruction=True)
-        return self.weight_matrix_argmax
+    def _render_lists(self, quantized):
+        if quantized and self.qvalid and getattr(self, "_qrecon_lists", None) is not None:
+            return self._qrecon_lists
+        if not quantized and self.valid and getattr(self, "_recon_lists", None) is not None:
+            return self._recon_lists
+        return self._lists
 
-    def get_qreconstruction(self):
-        if not self.qvalid:
-            self.run_batched(train=False, update_reconstruction=True, with_quantized_params=True)
-        return self.qreconstruction_image
+    def _render_grid(self, m):
+        shape, n = self.image.shape, self.batch_size_valued
+        grid = [int(shape[l]) // n[l] for l in range(self.dim_domain)]
+        extent = [g * ml for g, ml in zip(grid, m)]
+        return grid, extent, [blk.render_axis(int(shape[l]), extent[l]) for l in range(self.dim_domain)]
 
-    def get_qlosses(self):
-        return self.qlosses
-
-    def get_qmses(self):
-        return self.qmses
-
-    def get_psnr(self):
-        rec = self.get_reconstruction()
-        return float(-10.0 * np.log10(np.mean((rec.astype(np.float64) - self.image.astype(np.float64)) ** 2)))
-
-    def get_losses(self):
-        return self.losses
-
-    def get_mses(self):
-        return self.mses
-
-    def get_num_pis(self):
-        return self.num_pis
-
-    def get_num_svs(self):
-        return self.num_svs
-
-    def get_best_loss(self):
-        return self.best_loss
-
-    def get_best_mse(self):
-        return self.best_mse
-
-    def get_iter(self):
-        return self.iter
-
-    def get_original_image(self):
-        return np.squeeze(self.image)
+    def _engine_render(self, params, lists, axes, m, grid, extent, out, tdt, want_argmax):
+        return self._engine.render(params, lists, axes, m, first_batch=self.lo, out=out, dtype=tdt, want_argmax=want_argmax,
+                                   num_batches=self.hi - self.lo)

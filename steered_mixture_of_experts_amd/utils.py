@@ -7,10 +7,7 @@ import pickle
 
 import numpy as np
 
-
-def psnr(mse, precision):
-    """plotter.py:14-15: mse is mse_op, i.e. mean(diff^2) * (2^p)^2 (smoe.py:1053)."""
-    return 10 * np.log10((2 ** precision) ** 2 / mse)
+from .blocks import psnr  # noqa: F401  (plotter.py:14-15; re-exported, one definition)
 
 
 def save_model(smoe, path, best=False, reduce=False, quantize=False):

@@ -92,3 +92,68 @@ def test_get_batch_shape_divisor_search():
     assert s[-1] == 6 and (64 // s[0]) * (64 // s[1]) * (16 // s[2]) == 8 and s == (32, 32, 8, 6)
     s = blk.get_batch_shape(7, (30, 20, 4))                                   # 7 is not reachable: next is 8
     assert (30 // s[0]) * (20 // s[1]) == 8 and 30 % s[0] == 0 and 20 % s[1] == 0
+
+
+# what the engine constructors set themselves: everything else in the ctypes config structs comes from marshal_common
+_SET_BY_THE_CONSTRUCTOR = {"abi_version", "device", "block_shape", "image_shape", "batch_shape", "overlap"}
+
+
+def _distinct_config(cls, **shapes):
+    """A config whose every common field differs from its default and from every other field."""
+    import dataclasses
+    from steered_mixture_of_experts_amd import engine
+    kw, n = dict(shapes), 10
+    for f in dataclasses.fields(engine._CommonConfig):
+        n += 1
+        if f.name in ("bit_depths", "lower_bounds", "upper_bounds"):
+            kw[f.name] = tuple(type(f.default[0])(10 * n + i) for i in range(5))
+        elif f.type == "bool":
+            kw[f.name] = not f.default
+        else:
+            kw[f.name] = {"int": int, "float": float}[f.type](n) + (0.5 if f.type == "float" else 0)
+        assert kw[f.name] != f.default
+    return cls(**kw)
+
+
+def _field_bytes(c, name):
+    import ctypes as C
+    d = getattr(type(c), name)
+    return C.string_at(C.addressof(c) + d.offset, d.size)
+
+
+def test_marshalling_fills_every_field_of_both_config_structs():
+    """marshal_common is the one place a config object becomes a C struct: every field of SmoeConfig / SmoeSharedConfig
+    arrives (flags as 0 / 1, the tuples element by element), or is on the short list of the constructors' own fields --
+    a field added to the header and its ctypes mirror but forgotten in Python fails here."""
+    import ctypes as C
+    import dataclasses
+    from steered_mixture_of_experts_amd import _lib, engine
+    cases = [(engine.EngineConfig, _lib.SmoeConfig, {"block_shape": (16, 8, 4)}),
+             (engine.SharedConfig, _lib.SmoeSharedConfig, {"image_shape": (32, 48), "batch_shape": (16, 8), "overlap": 2})]
+    for cls, struct, shapes in cases:
+        cfg = _distinct_config(cls, **shapes)
+        c = engine.marshal_common(struct(), cfg)
+        assert c.dim == len(shapes.get("block_shape", shapes.get("image_shape")))
+        for name, ctype in struct._fields_:
+            if name in _SET_BY_THE_CONSTRUCTOR or name == "dim":
+                continue
+            want, got = getattr(cfg, name), getattr(c, name)          # a field the dataclass lacks raises here
+            if isinstance(want, tuple):
+                assert list(got) == [ctype._type_(v).value for v in want], name
+            elif isinstance(want, bool):
+                assert ctype is C.c_int32 and got == int(want), name
+            else:
+                assert got == ctype(want).value, name
+        seen = [getattr(c, name) for name, _ in struct._fields_ if name not in _SET_BY_THE_CONSTRUCTOR | {"dim"}]
+        flat = [v for x in seen for v in (list(x) if hasattr(x, "__len__") else [x]) if v not in (0, 1)]
+        assert len(flat) == len(set(flat)), "two fields carry the same value: a swap would go unseen"
+        # the flags are all 0 / 1: flip them one at a time, and exactly that struct field follows
+        for f in dataclasses.fields(cfg):
+            if f.type == "bool":
+                c2 = engine.marshal_common(struct(), dataclasses.replace(cfg, **{f.name: not getattr(cfg, f.name)}))
+                changed = [name for name, _ in struct._fields_ if bytes(_field_bytes(c, name)) != bytes(_field_bytes(c2, name))]
+                assert changed == [f.name]
+    # the conversions of the falsy values
+    cfg = engine.EngineConfig(block_shape=(16, 16), channels=1, kernels=4, start_pis=0, grad_clip=None)
+    c = engine.marshal_common(_lib.SmoeConfig(), cfg)
+    assert c.start_pis == 4 and c.grad_clip == 0.0
