@@ -218,6 +218,34 @@ int smoe_render(smoe_handle h, int32_t first_block, int32_t num_blocks, const sm
                 const float* const axis_coords[3], const int32_t samples[3], const int32_t grid[3],
                 const int64_t extent[3], void* image, int32_t image_format, uint8_t* argmax, void* stream);
 
+/* Seam-free decoder: smoe_render, with the models of neighbouring blocks cross-faded in a band around every block border.
+ * Every block is fitted alone, so the stitched function jumps at the borders; a fitted block is a continuous function and
+ * legal outside [0, 1], so near a border the neighbour is evaluated at the same image position too and the two (2^dim at a
+ * corner) are mixed with a partition-of-unity window that is 1/2 : 1/2 on the seam.  Arguments as smoe_render, except:
+ *   p, active                cover ALL prod(grid) blocks of the image, indexed by the image-wide block index (row-major over
+ *                            grid[]): the neighbours of the rendered range are read.  So does the centre grid of
+ *                            smoe_set_center_grid when the handle has one.  Only positions owned by
+ *                            [first_block, first_block + num_blocks) are written
+ *   blend[l]                 half-width of the band on axis l in SOURCE pixels, finite, 0 <= blend[l] <= block_shape[l] / 2;
+ *                            0 (or block_shape[l] == 1): no blending on that axis.  All zero: smoe_render's kernel runs
+ * Per axis, with n = block_shape[l], u the sample's coordinate, b = blend[l] / (n - 1), the seams of the own block at
+ * s0 = -0.5 / (n - 1) and s1 = 1 + 0.5 / (n - 1): the block at g + 1 gets w_hi = clamp(0.5 * (1 + (u - s1) / b), 0, 1), the block
+ * at g - 1 gets w_lo = clamp(0.5 * (1 + (s0 - u) / b), 0, 1), a block outside the image 0, the own block 1 - w_lo - w_hi.  The
+ * weight W of a block is the product over the axes.  Every block with W > 0 is evaluated at its own coordinate of the
+ * sample (fp32: u - n / (n - 1) seen from g + 1, u + n / (n - 1) from g - 1) exactly as smoe_render evaluates a block; blocks
+ * in which no kernel has influence on the sample are dropped (an extrapolated model often loses all its kernels to the
+ * threshold); the sample is sum W clip(y, 0, 1) / sum W over the rest, 0 if none is left, put on the lattice once
+ * (floor(v (2^precision - 1) + 1/2)).  Samples whose neighbour weights are all 0 are bit-identical to smoe_render's.
+ *   argmax                   of the own block only, as smoe_render
+ * Limits: with blend not all zero the samples per block may sum to at most 16384 over the axes (smoe_render: 32768), and
+ * the workgroup's tables, block records and staging must fit 160 KB of LDS like smoe_render's; beyond that the call returns
+ * SMOE_ERR_UNSUPPORTED.  The upper clamp of w_hi / w_lo at 1 only acts on coordinates that leave the own block's footprint by
+ * more than the band (blocks.render_axis never produces them); it keeps the own weight from going negative there. */
+int smoe_render_blend(smoe_handle h, int32_t first_block, int32_t num_blocks, const smoe_params* p, const uint32_t* active,
+                      const float* const axis_coords[3], const int32_t samples[3], const int32_t grid[3],
+                      const int64_t extent[3], const float blend[3], void* image, int32_t image_format, uint8_t* argmax,
+                      void* stream);
+
 /* Name of the kernel variant smoe_fit would launch for num_blocks (diagnostics / profiles). */
 const char* smoe_fit_variant(smoe_handle h, int32_t num_blocks);
 

@@ -772,62 +772,149 @@ int smoe_fit(smoe_handle h, int32_t num_blocks, const float* target, const float
     return check_debug_word(h, (hipStream_t)stream, "smoe_fit");
 }
 
-int smoe_render(smoe_handle h, int32_t first_block, int32_t num_blocks, const smoe_params* p, const uint32_t* active,
-                const float* const axis_coords[3], const int32_t samples[3], const int32_t grid[3],
-                const int64_t extent[3], void* image, int32_t image_format, uint8_t* argmax, void* stream) {
-    if (!h) return fail(SMOE_ERR_INVALID, "smoe_render: null handle");
-    if (first_block < 0 || num_blocks < 0) return fail(SMOE_ERR_INVALID, "smoe_render: negative first_block / num_blocks");
-    if (!params_ok(p)) return fail(SMOE_ERR_INVALID, "smoe_render: p (all six parameter tensors) is required");
-    if (!image) return fail(SMOE_ERR_INVALID, "smoe_render: image is required");
+namespace {
+
+// the argument checks smoe_render and smoe_render_blend share; `fn` = the entry point's name in the messages
+int render_check(smoe_handle h, const std::string& fn, int32_t first_block, int32_t num_blocks, const smoe_params* p,
+                 const float* const axis_coords[3], const int32_t samples[3], const int32_t grid[3],
+                 const int64_t extent[3], void* image, int32_t image_format) {
+    if (!h) return fail(SMOE_ERR_INVALID, fn + ": null handle");
+    if (first_block < 0 || num_blocks < 0) return fail(SMOE_ERR_INVALID, fn + ": negative first_block / num_blocks");
+    if (!params_ok(p)) return fail(SMOE_ERR_INVALID, fn + ": p (all six parameter tensors) is required");
+    if (!image) return fail(SMOE_ERR_INVALID, fn + ": image is required");
     if (!axis_coords || !samples || !grid || !extent)
-        return fail(SMOE_ERR_INVALID, "smoe_render: axis_coords, samples, grid and extent are required");
+        return fail(SMOE_ERR_INVALID, fn + ": axis_coords, samples, grid and extent are required");
     if (image_format != SMOE_IMAGE_F32 && image_format != SMOE_IMAGE_U8)
-        return fail(SMOE_ERR_INVALID, "smoe_render: image_format must be SMOE_IMAGE_F32 or SMOE_IMAGE_U8");
+        return fail(SMOE_ERR_INVALID, fn + ": image_format must be SMOE_IMAGE_F32 or SMOE_IMAGE_U8");
     const int D = h->cfg.dim;
     long long total = 1;
     for (int l = 0; l < D; ++l) {
         const std::string ax = "[" + std::to_string(l) + "]";
-        if (!axis_coords[l]) return fail(SMOE_ERR_INVALID, "smoe_render: axis_coords" + ax + " is null");
-        if (samples[l] < 1) return fail(SMOE_ERR_INVALID, "smoe_render: samples" + ax + " must be >= 1");
-        if (grid[l] < 1) return fail(SMOE_ERR_INVALID, "smoe_render: grid" + ax + " must be >= 1");
+        if (!axis_coords[l]) return fail(SMOE_ERR_INVALID, fn + ": axis_coords" + ax + " is null");
+        if (samples[l] < 1) return fail(SMOE_ERR_INVALID, fn + ": samples" + ax + " must be >= 1");
+        if (grid[l] < 1) return fail(SMOE_ERR_INVALID, fn + ": grid" + ax + " must be >= 1");
         if (extent[l] < 1 || extent[l] > (long long)grid[l] * samples[l])
-            return fail(SMOE_ERR_INVALID, "smoe_render: extent" + ax + " must be 1 .. grid * samples");
+            return fail(SMOE_ERR_INVALID, fn + ": extent" + ax + " must be 1 .. grid * samples");
         total *= grid[l];
-        if (total > 0x7fffffffLL) return fail(SMOE_ERR_INVALID, "smoe_render: grid has more than 2^31 blocks");
+        if (total > 0x7fffffffLL) return fail(SMOE_ERR_INVALID, fn + ": grid has more than 2^31 blocks");
     }
     if ((long long)first_block + num_blocks > total)
-        return fail(SMOE_ERR_INVALID, "smoe_render: first_block + num_blocks exceeds prod(grid)");
+        return fail(SMOE_ERR_INVALID, fn + ": first_block + num_blocks exceeds prod(grid)");
     if (image_format == SMOE_IMAGE_U8 && h->cfg.precision > 8)
-        return fail(SMOE_ERR_UNSUPPORTED, "smoe_render: SMOE_IMAGE_U8 needs precision <= 8");
-    if (num_blocks == 0) return SMOE_OK;
-    // the tiling -- and with it the hoisting level, i.e. the order of a sample's fused multiply-adds -- smoe_forward takes
-    // for this handle and this many blocks
-    const smoe::Variant* v = find_variant(h, num_blocks, false);
-    if (!v || !v->render) return fail(SMOE_ERR_UNSUPPORTED, "smoe_render: no kernel variant for this handle");
-    const int hl = h->cfg.ssim_opt ? 0 : hoist_level(h, v);
-    HIP_TRY(hipSetDevice(h->cfg.device), "hipSetDevice");
+        return fail(SMOE_ERR_UNSUPPORTED, fn + ": SMOE_IMAGE_U8 needs precision <= 8");
+    return SMOE_OK;
+}
+
+// the checked arguments as the kernels take them.  p / active / mus_grid: leading axis = the blocks of the call
+smoe::RenderArgs render_args(smoe_handle h, int32_t first_block, int32_t num_blocks, const smoe_params& p, const uint32_t* active,
+                             const float* mus_grid, const float* const axis_coords[3], const int32_t samples[3],
+                             const int32_t grid[3], const int64_t extent[3], void* image, int32_t image_format, uint8_t* argmax) {
+    const int D = h->cfg.dim;
     smoe::RenderArgs a;
     std::memset(&a, 0, sizeof a);
-    a.p = *p; a.active = active;
+    a.p = p; a.active = active;
     for (int l = 0; l < D; ++l) { a.ax[l] = axis_coords[l]; a.m[l] = samples[l]; a.grid[l] = grid[l]; a.ext[l] = extent[l]; }
     for (int l = D; l < SMOE_MAX_DIM; ++l) { a.m[l] = 1; a.grid[l] = 1; a.ext[l] = 1; }
     a.first = first_block; a.nb = num_blocks;
     a.image = image; a.fmt = image_format; a.argmax = argmax;
-    a.mus_grid = h->mus_grid;
+    a.mus_grid = mus_grid;
     a.vec_img = ((uintptr_t)image % 16 == 0) ? 1 : 0;
     a.vec_arg = ((uintptr_t)argmax % 16 == 0) ? 1 : 0;
     a.kc = h->kc;
-#if !SMOE_HOST_TEST
-    {
-        const hipError_t e = v->render(a, hl, v->G, (hipStream_t)stream);
-        if (e == hipErrorNotSupported)
-            return fail(SMOE_ERR_UNSUPPORTED, "smoe_render: this sample grid does not fit the kernel's LDS (or the graph variant is not built for the triple)");
-        if (e != hipSuccess) return fail_hip(e, "smoe_render launch");
-    }
-#else
-    (void)hl;
-#endif
+    return a;
+}
+
+// the kernel variant and hoisting level of a decode of num_blocks blocks: the tiling -- and with it the order of a sample's
+// fused multiply-adds -- smoe_forward takes for this handle and this many blocks
+int render_plan(smoe_handle h, const char* fn, int32_t num_blocks, const smoe::Variant** v, int* hl) {
+    *v = find_variant(h, num_blocks, false);
+    if (!*v || !(*v)->render || !(*v)->render_blend) return fail(SMOE_ERR_UNSUPPORTED, std::string(fn) + ": no kernel variant for this handle");
+    *hl = h->cfg.ssim_opt ? 0 : hoist_level(h, *v);
+    HIP_TRY(hipSetDevice(h->cfg.device), "hipSetDevice");
     return SMOE_OK;
+}
+
+int render_launched(const char* fn, hipError_t e) {
+    if (e == hipErrorNotSupported)
+        return fail(SMOE_ERR_UNSUPPORTED, std::string(fn) + ": this sample grid does not fit the kernel's LDS (or the graph variant is not built for the triple)");
+    if (e != hipSuccess) return fail_hip(e, (std::string(fn) + " launch").c_str());
+    return SMOE_OK;
+}
+
+// launch render_kernel for checked arguments
+int render_launch(smoe_handle h, const char* fn, const smoe::RenderArgs& a, void* stream) {
+    const smoe::Variant* v = nullptr;
+    int hl = 0;
+    const int rc = render_plan(h, fn, a.nb, &v, &hl);
+    if (rc != SMOE_OK) return rc;
+#if !SMOE_HOST_TEST
+    return render_launched(fn, v->render(a, hl, v->G, (hipStream_t)stream));
+#else
+    (void)stream;
+    return SMOE_OK;
+#endif
+}
+
+}  // namespace
+
+int smoe_render(smoe_handle h, int32_t first_block, int32_t num_blocks, const smoe_params* p, const uint32_t* active,
+                const float* const axis_coords[3], const int32_t samples[3], const int32_t grid[3],
+                const int64_t extent[3], void* image, int32_t image_format, uint8_t* argmax, void* stream) {
+    const int rc = render_check(h, "smoe_render", first_block, num_blocks, p, axis_coords, samples, grid, extent, image, image_format);
+    if (rc != SMOE_OK) return rc;
+    if (num_blocks == 0) return SMOE_OK;
+    return render_launch(h, "smoe_render", render_args(h, first_block, num_blocks, *p, active, h->mus_grid, axis_coords, samples,
+                                                      grid, extent, image, image_format, argmax), stream);
+}
+
+int smoe_render_blend(smoe_handle h, int32_t first_block, int32_t num_blocks, const smoe_params* p, const uint32_t* active,
+                      const float* const axis_coords[3], const int32_t samples[3], const int32_t grid[3],
+                      const int64_t extent[3], const float blend[3], void* image, int32_t image_format, uint8_t* argmax,
+                      void* stream) {
+    const char* fn = "smoe_render_blend";
+    const int rc = render_check(h, fn, first_block, num_blocks, p, axis_coords, samples, grid, extent, image, image_format);
+    if (rc != SMOE_OK) return rc;
+    if (!blend) return fail(SMOE_ERR_INVALID, std::string(fn) + ": blend is required");
+    const int D = h->cfg.dim, K = h->cfg.kernels, Cn = h->cfg.channels;
+    bool any = false;
+    for (int l = 0; l < D; ++l) {
+        const int n = h->cfg.block_shape[l];
+        if (!std::isfinite(blend[l]) || blend[l] < 0.0f || blend[l] > 0.5f * (float)n)
+            return fail(SMOE_ERR_INVALID, std::string(fn) + ": blend[" + std::to_string(l) + "] must be finite and within 0 .. block_shape / 2");
+        any = any || (blend[l] > 0.0f && n > 1);
+    }
+    if (num_blocks == 0) return SMOE_OK;
+    if (!any) {
+        // nothing to blend: smoe_render's kernel on the shard's slice of the image-wide arrays
+        const size_t o = (size_t)first_block * K;
+        smoe_params q = *p;
+        q.pis += o; q.musX += o * D; q.A_diagonal += o * D * D; q.A_corr += o * D * D; q.gamma_e += o * D * Cn; q.nu_e += o * Cn;
+        return render_launch(h, fn, render_args(h, first_block, num_blocks, q, active ? active + first_block : nullptr,
+                                               h->mus_grid ? h->mus_grid + o * D : nullptr, axis_coords, samples, grid, extent,
+                                               image, image_format, argmax), stream);
+    }
+    // the own block's samples must come out as smoe_render's for this many blocks: the same tiling, the same hoisting level
+    const smoe::Variant* v = nullptr;
+    int hl = 0;
+    const int rp = render_plan(h, fn, num_blocks, &v, &hl);
+    if (rp != SMOE_OK) return rp;
+    smoe::RenderBlendArgs b;
+    std::memset(&b, 0, sizeof b);
+    b.r = render_args(h, first_block, num_blocks, *p, active, h->mus_grid, axis_coords, samples, grid, extent, image, image_format, argmax);
+    for (int l = 0; l < D; ++l) {
+        const int n = h->cfg.block_shape[l];
+        if (n < 2) continue;                               // one pixel per block on this axis: no pitch, nothing to blend
+        b.s0[l] = (float)(-0.5 / (n - 1));
+        b.s1[l] = (float)(1.0 + 0.5 / (n - 1));
+        b.band[l] = (float)((double)blend[l] / (n - 1));
+        b.pitch[l] = (float)((double)n / (n - 1));
+    }
+#if !SMOE_HOST_TEST
+    return render_launched(fn, v->render_blend(b, hl, v->G, (hipStream_t)stream));
+#else
+    (void)stream;
+    return SMOE_OK;
+#endif
 }
 
 int smoe_update_kernel_list(smoe_handle h, int32_t num_blocks, const smoe_params* p,

@@ -148,6 +148,16 @@ struct RenderArgs {
     KernelConsts kc;
 };
 
+// smoe_render_blend (smoe_render_blend.hip.h): smoe_render with a cross-fade towards the neighbouring blocks around every
+// block border.  r.p / r.active / r.mus_grid cover ALL prod(grid) blocks and are indexed by the image-wide block index.
+struct RenderBlendArgs {
+    RenderArgs r;
+    float s0[SMOE_MAX_DIM], s1[SMOE_MAX_DIM];   // the own block's seams in block units: -0.5 / (n - 1), 1 + 0.5 / (n - 1)
+    float band[SMOE_MAX_DIM];                   // half-width of the blend band in block units, blend / (n - 1); 0: none on this axis
+    float pitch[SMOE_MAX_DIM];                  // one block in block units, n / (n - 1)
+    int off_w;                                  // float offset of the neighbour-weight tables in the dynamic LDS (launcher)
+};
+
 // The graph a fit or evaluation launch runs; with the tiling (Variant) it names one kernel instantiation
 // (resolve_fit / resolve_fwd in smoe_block.hip.h).
 struct Graph {
@@ -177,6 +187,8 @@ struct Variant {
     int (*duo_waves_per_cu)(int N, bool has_lw, int hoist_level);
     // decoder (smoe_render.hip.h; the same entry on every tiling of a triple): hl = hoisting level, lanes = the tiling's G
     hipError_t (*render)(const RenderArgs&, int hl, int lanes, hipStream_t);
+    // seam-free decoder (smoe_render_blend.hip.h), same conventions
+    hipError_t (*render_blend)(const RenderBlendArgs&, int hl, int lanes, hipStream_t);
 };
 
 // ---- shared-kernel image mode (smoe_shared.hip) ----------------------------------------------

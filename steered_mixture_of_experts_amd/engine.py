@@ -9,6 +9,7 @@ import ctypes as C
 import dataclasses
 from typing import Dict, Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -322,6 +323,52 @@ class BlockEngine(_Engine):
             _lib.check(self.lib.smoe_render(self._h, int(first_block), B, C.byref(cp), _ptr(active), tabs, m3,
                                             _slots(C.c_int32, grid, 1), _slots(C.c_int64, extent, 1),
                                             _ptr(out), fmt, _ptr(am), self._stream()))
+        return (out, am) if want_argmax else out
+
+    def render_blend(self, params, active, axes, grid, extent, blend, first_block=0, num_blocks=None, out=None,
+                     dtype=torch.float32, want_argmax=False, center_grid=None):
+        """Seam-free decode (include/smoe_hip.h: smoe_render_blend): ``render``, with the neighbouring blocks' models
+        cross-faded in a band of ``blend[l]`` source pixels (half-width, ``0 .. block_shape[l] / 2``) around every block
+        border.  Unlike ``render``, ``params`` and ``active`` cover ALL ``prod(grid)`` blocks of the image -- the neighbours
+        of the rendered range ``[first_block, first_block + num_blocks)`` (default: up to the last block) are read --
+        and so does ``center_grid`` [prod(grid), K, d], the image-wide kernel grid of a use_diff_center model whose
+        engine holds a shard's grid (it is put back afterwards).  Returns what ``render`` returns."""
+        d = self.cfg.dim
+        total = 1
+        for g in grid:
+            total *= int(g)
+        self._check_params(params, total)
+        self._check_render_dtype(dtype)
+        if len(axes) != d or len(grid) != d or len(extent) != d:
+            raise ValueError(f"render_blend: axes, grid and extent need {d} entries")
+        for t in axes:
+            if t.numel() < 1 or not self._is_axis_table(t):
+                raise ValueError(f"render_blend: every axis table must be a contiguous 1-d float32 tensor on {self.device}")
+        bl = [float(v) for v in np.atleast_1d(blend)]
+        bl = bl * d if len(bl) == 1 else bl
+        if len(bl) != d:
+            raise ValueError(f"render_blend: blend needs one value or {d}")
+        grid = [int(g) for g in grid]
+        extent = [int(e) for e in extent]
+        B = total - int(first_block) if num_blocks is None else int(num_blocks)
+        if active is not None and (tuple(active.shape) != (total,) or active.dtype != torch.int32 or active.device != self.device):
+            raise ValueError(f"render_blend: active must be int32 [{total}] on {self.device}")
+        out, fmt = self._render_out(out, extent, dtype, everything=(first_block == 0 and B == total))
+        am = torch.full(tuple(extent), 255, dtype=torch.uint8, device=self.device) if want_argmax else None
+        if B > 0:
+            cp = self._cparams(params)
+            tabs = _slots(C.c_void_p, [t.data_ptr() for t in axes], None)
+            m3 = _slots(C.c_int32, [int(t.numel()) for t in axes], 1)
+            held = getattr(self, "_center_grid", None)
+            if center_grid is not None:
+                self.set_center_grid(center_grid)
+            try:
+                _lib.check(self.lib.smoe_render_blend(self._h, int(first_block), B, C.byref(cp), _ptr(active), tabs, m3,
+                                                      _slots(C.c_int32, grid, 1), _slots(C.c_int64, extent, 1),
+                                                      _slots(C.c_float, bl, 0.0), _ptr(out), fmt, _ptr(am), self._stream()))
+            finally:
+                if center_grid is not None:
+                    self.set_center_grid(held)
         return (out, am) if want_argmax else out
 
     def fit(self, target, params, state: AdamState, active, n_iters: int, loss_w=None, diverged=None,

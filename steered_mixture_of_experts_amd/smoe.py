@@ -291,10 +291,10 @@ class _SmoeBase:
         return {k: torch.from_numpy(v).to(self._engine.device) for k, v in self._local_rparams().items()}
 
     # -- decoding on another grid -------------------------------------------------------------
-    def _render(self, scale, samples_per_block, dtype, quantized, want_argmax, to_host, use_lists=True):
+    def _render(self, scale, samples_per_block, dtype, quantized, want_argmax, to_host, use_lists=True, blend=None):
         """``render`` of both modes.  Hooks: ``_local_rparams``, ``_render_lists(quantized)``, ``_render_grid(m)`` ->
         (tile grid, output extent, one sample table per axis), ``_engine_render`` and, with ``_block_local_ids``,
-        ``_global_ids``."""
+        ``_global_ids``.  ``blend``: None, or the per-axis half-widths (not all zero) for ``_engine_render_blend``."""
         d, n = self.dim_domain, self.batch_size_valued
         if scale is not None and samples_per_block is not None:
             raise ValueError("render: give scale or samples_per_block, not both")
@@ -325,7 +325,10 @@ class _SmoeBase:
         grid, extent, axes = self._render_grid(m)
         axes = [torch.from_numpy(a).to(dev) for a in axes]
         out = torch.zeros(tuple(extent) + (self.channels,), dtype=tdt, device=dev) if multi else None
-        res = self._engine_render(params, lists, axes, m, grid, extent, out, tdt, want_argmax)
+        if blend is None:
+            res = self._engine_render(params, lists, axes, m, grid, extent, out, tdt, want_argmax)
+        else:
+            res = self._engine_render_blend(params, lists, axes, grid, extent, out, tdt, want_argmax, blend)
         img, ids = res if want_argmax else (res, None)
         if ids is not None:
             ids = ids.to(torch.int64)
@@ -774,10 +777,16 @@ class Smoe(_SmoeBase):
         return self._gather_params(self._best)
 
     def render(self, scale=None, samples_per_block=None, dtype=np.float32, quantized=False, want_argmax=False,
-               to_host=True):
+               to_host=True, blend=0.0):
         """Decode the fitted blocks on another sampling grid, on the device (the engine's ``render``): every block is a
         continuous function of the coordinate, so zooming, a finer pitch or frames between the fitted ones are "evaluate
         the same model somewhere else" -- no pixel is interpolated.
+        ``blend``: a number or one per axis, in source pixels (``0 .. n_l / 2``).  Every block is fitted alone, so the
+        stitched function jumps at the block borders -- a grid of seams at 2x or 4x.  With ``blend > 0`` the neighbouring
+        block's model is evaluated too within ``blend`` pixels of a border and the two (2^d at a corner) are cross-faded,
+        1/2 : 1/2 on the seam (the engine's ``render_blend``; include/smoe_hip.h: smoe_render_blend): one continuous
+        function from the same fitted models.  Samples farther than ``blend`` from every border are unchanged, and so is
+        the kernel map of ``want_argmax``.  0 (the default) is the plain decoder.
         ``scale``: a number or one per axis, ``m_l = round(scale_l * n_l)`` samples per block (at least 1);
         ``samples_per_block``: the ``m_l`` themselves (a number or one per axis); neither: the training lattice.
         Sample positions: ``blocks.render_axis``.  Output extent ``E_l = image.shape[l] * m_l // n_l`` (the padding of a
@@ -787,9 +796,34 @@ class Smoe(_SmoeBase):
         ``get_weight_matrix_argmax``; -1 where no kernel has influence on the sample).  ``to_host=False`` returns device
         tensors.  Several ranks: every rank renders its blocks and the images are summed; the result is the same on
         every rank and for every number of ranks."""
-        return self._render(scale, samples_per_block, dtype, quantized, want_argmax, to_host)
+        d = self.dim_domain
+        bl = [float(v) for v in np.atleast_1d(blend)]
+        bl = bl * d if len(bl) == 1 else bl
+        if len(bl) != d:
+            raise ValueError(f"render: blend needs one value or {d}")
+        for v, nl in zip(bl, self.batch_size_valued):
+            if not np.isfinite(v) or v < 0 or v > nl / 2:
+                raise ValueError("render: blend must lie within 0 .. block size / 2 on every axis")
+        return self._render(scale, samples_per_block, dtype, quantized, want_argmax, to_host,
+                            blend=bl if any(v > 0 for v in bl) else None)
 
     # hooks of _render
+    def _engine_render_blend(self, params, active, axes, grid, extent, out, tdt, want_argmax, blend):
+        # the engine reads the neighbours of this rank's blocks: with several ranks, everyone's parameters and list words
+        # (small: a few hundred bytes per block) are gathered first; the images are summed as for blend = 0
+        center = None
+        if self.world_size > 1:
+            dev = self._engine.device
+            full = lambda t: torch.from_numpy(np.ascontiguousarray(sdist.allgather_blocks(t.cpu().numpy(), self.num_blocks))).to(dev)
+            params = {k: full(v) for k, v in params.items()}
+            active = None if active is None else full(active)
+            if self._mus_grid is not None and int(self.quantization_mode) >= 2:
+                center = torch.from_numpy(np.ascontiguousarray(sdist.allgather_blocks(self._mus_grid, self.num_blocks),
+                                                               dtype=np.float32)).to(dev)
+        return self._engine.render_blend(params, active, axes, grid, extent, blend, first_block=self.lo,
+                                         num_blocks=self.hi - self.lo, out=out, dtype=tdt, want_argmax=want_argmax,
+                                         center_grid=center)
+
     def _local_rparams(self):
         rp = {k: np.ascontiguousarray(self.rparams[k][self.lo:self.hi], dtype=np.float32) for k in PARAM_NAMES}
         return _pad_kernels(rp, self._kp)
@@ -1070,7 +1104,7 @@ class SharedSmoe(_SmoeBase):
         return self._host_params(self._best)
 
     def render(self, scale=None, samples_per_block=None, dtype=np.float32, quantized=False, want_argmax=False,
-               to_host=True, use_lists=True):
+               to_host=True, use_lists=True, blend=0.0):
         """Decode the fitted whole-image model on another sampling grid, on the device (the engine's ``render``).  The
         model is ONE continuous function over the image domain -- no block seams -- so zooming, a finer pitch or frames
         between the fitted ones are "evaluate the same model somewhere else"; no pixel is interpolated.
@@ -1092,7 +1126,10 @@ class SharedSmoe(_SmoeBase):
         free of the list boundaries.  (It is not the same function even on the training lattice: a pruned kernel's masked
         weight was zero, but its gate still sat in the normaliser of the pass that pruned it.)
         Several ranks: every rank renders its batches and the images are summed; the result is the same on every rank
-        and for every number of ranks."""
+        and for every number of ranks.
+        ``blend``: accepted for symmetry with ``Smoe.render`` and must be 0 -- a whole-image model has no block seams."""
+        if np.any(np.asarray(blend, dtype=np.float64) != 0):
+            raise ValueError("render: blend is for block models; a whole-image model has no block seams")
         return self._render(scale, samples_per_block, dtype, quantized, want_argmax, to_host, use_lists)
 
     # hooks of _render

@@ -6,6 +6,8 @@
 ``--scale S`` (one value or one per axis) / ``--frames F`` (samples per block on the time axis of video input) decode the
 model on another sampling grid with ``Smoe.render`` / ``SharedSmoe.render`` (per-block and whole-image pickles alike; on
 the device, written straight into the stitched image); with the defaults the output is the reference's.
+``--blend B`` (source pixels, one value or one per axis; per-block models only) cross-fades neighbouring blocks within ``B``
+pixels of every block border (``Smoe.render(blend=...)``): no block seams in the enlarged image.
 """
 import argparse
 import os
@@ -38,7 +40,7 @@ _shared_engine_factory = None      # tests put the oracle-backed engine here; No
 
 
 def main(image_path, results_path, params_file, batches=1, bit_depths=(20, 18, 6, 10, 10), quant_params=False,
-         scale=None, frames=None):
+         scale=None, frames=None, blend=None):
     if len(bit_depths) != 5:
         raise ValueError("Number of bit depths must be five!")           # smoe_reconstruction.py:17-18
     orig, precision, _ = read_image(image_path)
@@ -81,7 +83,8 @@ def main(image_path, results_path, params_file, batches=1, bit_depths=(20, 18, 6
     else:
         reconstruction = smoe.get_reconstruction()
     sc = [float(v) for v in np.atleast_1d(1.0 if scale is None else scale)]
-    if frames is not None or any(v != 1.0 for v in sc):
+    bl = [float(v) for v in np.atleast_1d(0.0 if blend is None else blend)]
+    if frames is not None or any(v != 1.0 for v in sc) or any(v != 0.0 for v in bl):
         # another sampling grid: evaluate the model there (Smoe.render / SharedSmoe.render); the pass above keeps loss / mse
         # as reported
         d = smoe.dim_domain
@@ -93,13 +96,15 @@ def main(image_path, results_path, params_file, batches=1, bit_depths=(20, 18, 6
         m = [max(1, int(round(v * n))) for v, n in zip(sc, smoe.batch_size_valued)]
         if frames is not None:
             m[2] = int(frames)
-        reconstruction = smoe.render(samples_per_block=m, quantized=with_q)
+        reconstruction = smoe.render(samples_per_block=m, quantized=with_q, blend=bl)
         reconstruction_path += "_" + "x".join(str(v) for v in m)
+        if any(v != 0.0 for v in bl):
+            reconstruction_path += "_blend" + "x".join("%g" % v for v in bl)
     write_image(reconstruction, reconstruction_path, smoe.dim_domain, smoe.use_yuv, precision)
     return reconstruction, loss, mse
 
 
-def _cli():
+def _parser():
     parser = argparse.ArgumentParser()
     parser.add_argument('-i', '--image_path', type=str, required=True, help="input image")
     parser.add_argument('-r', '--results_path', type=str, required=True, help="results path")
@@ -110,7 +115,14 @@ def _cli():
     parser.add_argument('--scale', type=float, default=None, nargs='+',
                         help="render at this scale (one value or one per axis; default 1 = the training lattice)")
     parser.add_argument('--frames', type=int, default=None, help="video: samples per block on the time axis")
-    args = parser.parse_args()
+    parser.add_argument('--blend', type=float, default=None, nargs='+',
+                        help="cross-fade neighbouring blocks within this many source pixels of a block border (one value or "
+                             "one per axis, at most half a block; default 0 = off; per-block models only)")
+    return parser
+
+
+def _cli(argv=None):
+    args = _parser().parse_args(argv)
     main(**vars(args))
 
 
