@@ -2653,7 +2653,8 @@ int fit_occupancy(int N, bool has_lw, int hoist, bool pair) {
       &fit_occupancy<D, C, K, G, W, (FULL) != 0>, &launch_readmit_quant<D, C, K, G, W>, \
       team_fit_ptr<D, C, K, G, W>(), team_lds_ptr<D, C, K, G, W>(), team_occ_ptr<D, C, K, G, W>(), \
       duo_fit_ptr<D, C, K, G>(), duo_lds_ptr<D, C, K, G>(), duo_occ_ptr<D, C, K, G>(), \
-      &launch_render<D, C, K, (SMOE_FULL != 0)>, &launch_render_blend<D, C, K, (SMOE_FULL != 0)> }
+      &launch_render<D, C, K, (SMOE_FULL != 0)>, &launch_render_blend<D, C, K, (SMOE_FULL != 0)>, \
+      &render_layout<D, C, K, (SMOE_FULL != 0)>, &render_blend_layout<D, C, K, (SMOE_FULL != 0)> }
 
 }  // namespace smoe
 #endif

@@ -101,6 +101,15 @@ bool params_ok(const smoe_params* p) {
     return p && p->pis && p->musX && p->A_diagonal && p->A_corr && p->gamma_e && p->nu_e;
 }
 
+// the output planes of a decode and the constants of the handle, as the three kernels take them (RenderArgs / SharedRenderArgs)
+template <typename Args, typename Id>
+void decoder_planes(Args& a, void* image, int32_t image_format, Id* argmax, const smoe::KernelConsts& kc) {
+    a.image = image; a.fmt = image_format; a.argmax = argmax;
+    a.vec_img = ((uintptr_t)image % 16 == 0) ? 1 : 0;
+    a.vec_arg = ((uintptr_t)argmax % 16 == 0) ? 1 : 0;
+    a.kc = kc;
+}
+
 // ssim_opt: per axis the b x b matrix of "SYMMETRIC pad by 5, correlate with the 11-tap Gaussian, VALID"
 // (smoe.py:993-996; image_ops_impl.py:132-149: softmax of -0.5 (a-5)^2 / 1.5^2, separable):
 // T[i][j] = sum_a g[a] [mirror(i + a - 5) == j], stored banded: out[i][a] = T[i][i + a - 5], 0 outside the axis
@@ -774,35 +783,52 @@ int smoe_fit(smoe_handle h, int32_t num_blocks, const float* target, const float
 
 namespace {
 
-// the argument checks smoe_render and smoe_render_blend share; `fn` = the entry point's name in the messages
-int render_check(smoe_handle h, const std::string& fn, int32_t first_block, int32_t num_blocks, const smoe_params* p,
-                 const float* const axis_coords[3], const int32_t samples[3], const int32_t grid[3],
-                 const int64_t extent[3], void* image, int32_t image_format) {
-    if (!h) return fail(SMOE_ERR_INVALID, fn + ": null handle");
-    if (first_block < 0 || num_blocks < 0) return fail(SMOE_ERR_INVALID, fn + ": negative first_block / num_blocks");
+// The argument checks smoe_render, smoe_render_blend and smoe_shared_render share, in the order the entry points have always
+// made them; `fn` = the entry point's name in the messages.  block_grid: the call brings its own block grid -- grid, extent and
+// the range [.., last_block) are checked with the axes (shared mode: the handle's batch grid, checked by check_range).
+// u8_code: the answer to SMOE_IMAGE_U8 on a lattice of more than 8 bits.  Block mode has returned SMOE_ERR_UNSUPPORTED there
+// and shared mode SMOE_ERR_INVALID since each was written, and callers may test for the code: the difference stays.
+int decoder_check(const std::string& fn, int u8_code, int D, int precision, const smoe_params* p,
+                  const float* const axis_coords[3], const int32_t samples[3], bool block_grid, const int32_t grid[3],
+                  const int64_t extent[3], long long last_block, void* image, int32_t image_format) {
     if (!params_ok(p)) return fail(SMOE_ERR_INVALID, fn + ": p (all six parameter tensors) is required");
     if (!image) return fail(SMOE_ERR_INVALID, fn + ": image is required");
-    if (!axis_coords || !samples || !grid || !extent)
-        return fail(SMOE_ERR_INVALID, fn + ": axis_coords, samples, grid and extent are required");
+    if (!axis_coords || !samples || (block_grid && (!grid || !extent)))
+        return fail(SMOE_ERR_INVALID, fn + (block_grid ? ": axis_coords, samples, grid and extent are required"
+                                                       : ": axis_coords and samples are required"));
     if (image_format != SMOE_IMAGE_F32 && image_format != SMOE_IMAGE_U8)
         return fail(SMOE_ERR_INVALID, fn + ": image_format must be SMOE_IMAGE_F32 or SMOE_IMAGE_U8");
-    const int D = h->cfg.dim;
     long long total = 1;
     for (int l = 0; l < D; ++l) {
         const std::string ax = "[" + std::to_string(l) + "]";
         if (!axis_coords[l]) return fail(SMOE_ERR_INVALID, fn + ": axis_coords" + ax + " is null");
         if (samples[l] < 1) return fail(SMOE_ERR_INVALID, fn + ": samples" + ax + " must be >= 1");
+        if (!block_grid) continue;
         if (grid[l] < 1) return fail(SMOE_ERR_INVALID, fn + ": grid" + ax + " must be >= 1");
         if (extent[l] < 1 || extent[l] > (long long)grid[l] * samples[l])
             return fail(SMOE_ERR_INVALID, fn + ": extent" + ax + " must be 1 .. grid * samples");
         total *= grid[l];
         if (total > 0x7fffffffLL) return fail(SMOE_ERR_INVALID, fn + ": grid has more than 2^31 blocks");
     }
-    if ((long long)first_block + num_blocks > total)
-        return fail(SMOE_ERR_INVALID, fn + ": first_block + num_blocks exceeds prod(grid)");
-    if (image_format == SMOE_IMAGE_U8 && h->cfg.precision > 8)
-        return fail(SMOE_ERR_UNSUPPORTED, fn + ": SMOE_IMAGE_U8 needs precision <= 8");
+    if (block_grid && last_block > total) return fail(SMOE_ERR_INVALID, fn + ": first_block + num_blocks exceeds prod(grid)");
+    if (image_format == SMOE_IMAGE_U8 && precision > 8) return fail(u8_code, fn + ": SMOE_IMAGE_U8 needs precision <= 8");
     return SMOE_OK;
+}
+
+// what a decoder's launcher answered, as a return code; `unsupported`: what hipErrorNotSupported means for this entry point
+int decoder_launched(const std::string& fn, hipError_t e, const char* unsupported) {
+    if (e == hipErrorNotSupported) return fail(SMOE_ERR_UNSUPPORTED, fn + ": " + unsupported);
+    if (e != hipSuccess) return fail_hip(e, (fn + " launch").c_str());
+    return SMOE_OK;
+}
+
+int render_check(smoe_handle h, const std::string& fn, int32_t first_block, int32_t num_blocks, const smoe_params* p,
+                 const float* const axis_coords[3], const int32_t samples[3], const int32_t grid[3],
+                 const int64_t extent[3], void* image, int32_t image_format) {
+    if (!h) return fail(SMOE_ERR_INVALID, fn + ": null handle");
+    if (first_block < 0 || num_blocks < 0) return fail(SMOE_ERR_INVALID, fn + ": negative first_block / num_blocks");
+    return decoder_check(fn, SMOE_ERR_UNSUPPORTED, h->cfg.dim, h->cfg.precision, p, axis_coords, samples, true, grid, extent,
+                         (long long)first_block + num_blocks, image, image_format);
 }
 
 // the checked arguments as the kernels take them.  p / active / mus_grid: leading axis = the blocks of the call
@@ -816,11 +842,8 @@ smoe::RenderArgs render_args(smoe_handle h, int32_t first_block, int32_t num_blo
     for (int l = 0; l < D; ++l) { a.ax[l] = axis_coords[l]; a.m[l] = samples[l]; a.grid[l] = grid[l]; a.ext[l] = extent[l]; }
     for (int l = D; l < SMOE_MAX_DIM; ++l) { a.m[l] = 1; a.grid[l] = 1; a.ext[l] = 1; }
     a.first = first_block; a.nb = num_blocks;
-    a.image = image; a.fmt = image_format; a.argmax = argmax;
     a.mus_grid = mus_grid;
-    a.vec_img = ((uintptr_t)image % 16 == 0) ? 1 : 0;
-    a.vec_arg = ((uintptr_t)argmax % 16 == 0) ? 1 : 0;
-    a.kc = h->kc;
+    decoder_planes(a, image, image_format, argmax, h->kc);
     return a;
 }
 
@@ -834,12 +857,8 @@ int render_plan(smoe_handle h, const char* fn, int32_t num_blocks, const smoe::V
     return SMOE_OK;
 }
 
-int render_launched(const char* fn, hipError_t e) {
-    if (e == hipErrorNotSupported)
-        return fail(SMOE_ERR_UNSUPPORTED, std::string(fn) + ": this sample grid does not fit the kernel's LDS (or the graph variant is not built for the triple)");
-    if (e != hipSuccess) return fail_hip(e, (std::string(fn) + " launch").c_str());
-    return SMOE_OK;
-}
+// what hipErrorNotSupported of a block decoder's launcher means
+const char* const kRenderUnsupported = "this sample grid does not fit the kernel's LDS (or the graph variant is not built for the triple)";
 
 // launch render_kernel for checked arguments
 int render_launch(smoe_handle h, const char* fn, const smoe::RenderArgs& a, void* stream) {
@@ -848,10 +867,12 @@ int render_launch(smoe_handle h, const char* fn, const smoe::RenderArgs& a, void
     const int rc = render_plan(h, fn, a.nb, &v, &hl);
     if (rc != SMOE_OK) return rc;
 #if !SMOE_HOST_TEST
-    return render_launched(fn, v->render(a, hl, v->G, (hipStream_t)stream));
+    return decoder_launched(fn, v->render(a, hl, v->G, (hipStream_t)stream), kRenderUnsupported);
 #else
     (void)stream;
-    return SMOE_OK;
+    smoe::RenderArgs g = a;                                // everything but the launch: the geometry
+    smoe::RenderLayout lay;
+    return decoder_launched(fn, v->render_layout(g, hl, v->G, lay), kRenderUnsupported);
 #endif
 }
 
@@ -910,10 +931,11 @@ int smoe_render_blend(smoe_handle h, int32_t first_block, int32_t num_blocks, co
         b.pitch[l] = (float)((double)n / (n - 1));
     }
 #if !SMOE_HOST_TEST
-    return render_launched(fn, v->render_blend(b, hl, v->G, (hipStream_t)stream));
+    return decoder_launched(fn, v->render_blend(b, hl, v->G, (hipStream_t)stream), kRenderUnsupported);
 #else
     (void)stream;
-    return SMOE_OK;
+    smoe::RenderLayout lay;
+    return decoder_launched(fn, v->render_blend_layout(b, hl, v->G, lay), kRenderUnsupported);
 #endif
 }
 
@@ -1261,22 +1283,13 @@ int smoe_shared_forward(smoe_shared_handle h, int32_t first_batch, int32_t num_b
 int smoe_shared_render(smoe_shared_handle h, int32_t first_batch, int32_t num_batches, const smoe_params* p,
                        const uint32_t* lists, const float* const axis_coords[3], const int32_t samples[3],
                        void* image, int32_t image_format, int32_t* argmax, void* stream) {
+    const char* fn = "smoe_shared_render";
     if (!h) return fail(SMOE_ERR_INVALID, "smoe_shared_render: null handle");
-    int rc = check_range(h, first_batch, num_batches, "smoe_shared_render");
+    int rc = check_range(h, first_batch, num_batches, fn);
     if (rc) return rc;
-    if (!params_ok(p)) return fail(SMOE_ERR_INVALID, "smoe_shared_render: p (all six parameter tensors) is required");
-    if (!image) return fail(SMOE_ERR_INVALID, "smoe_shared_render: image is required");
-    if (!axis_coords || !samples) return fail(SMOE_ERR_INVALID, "smoe_shared_render: axis_coords and samples are required");
-    if (image_format != SMOE_IMAGE_F32 && image_format != SMOE_IMAGE_U8)
-        return fail(SMOE_ERR_INVALID, "smoe_shared_render: image_format must be SMOE_IMAGE_F32 or SMOE_IMAGE_U8");
     const int D = h->cfg.dim;
-    for (int l = 0; l < D; ++l) {
-        const std::string ax = "[" + std::to_string(l) + "]";
-        if (!axis_coords[l]) return fail(SMOE_ERR_INVALID, "smoe_shared_render: axis_coords" + ax + " is null");
-        if (samples[l] < 1) return fail(SMOE_ERR_INVALID, "smoe_shared_render: samples" + ax + " must be >= 1");
-    }
-    if (image_format == SMOE_IMAGE_U8 && h->cfg.precision > 8)
-        return fail(SMOE_ERR_INVALID, "smoe_shared_render: SMOE_IMAGE_U8 needs precision <= 8");
+    rc = decoder_check(fn, SMOE_ERR_INVALID, D, h->cfg.precision, p, axis_coords, samples, false, nullptr, nullptr, 0, image, image_format);
+    if (rc) return rc;
     if (num_batches == 0) return SMOE_OK;
     rc = shared_check_abort(h, "smoe_shared_render");
     if (rc) return rc;
@@ -1291,22 +1304,15 @@ int smoe_shared_render(smoe_shared_handle h, int32_t first_batch, int32_t num_ba
         a.ext[l] = (long long)a.grid[l] * a.m[l];
     }
     a.b0 = first_batch; a.nb = num_batches; a.K = h->cfg.kernels; a.KW = h->KW;
-    a.image = image; a.fmt = image_format; a.argmax = argmax;
-    a.vec_img = ((uintptr_t)image % 16 == 0) ? 1 : 0;
-    a.vec_arg = ((uintptr_t)argmax % 16 == 0) ? 1 : 0;
     a.qrng = h->d_qrng; a.mus_grid = h->mus_grid;
-    a.kc = h->kc;
+    decoder_planes(a, image, image_format, argmax, h->kc);
     // SMOE_SHARED_RENDER_SPLIT=n: n workgroups per batch instead of the automatic choice (tuning / test hook; the image does
     // not depend on it)
     int split_hint = 0;
     if (const char* v = std::getenv("SMOE_SHARED_RENDER_SPLIT")) split_hint = std::atoi(v);
     HIP_TRY(refresh_ranges(h, p, (hipStream_t)stream), "smoe_shared_render ranges");
-    {
-        const hipError_t e = smoe::launch_shared_render(a, D, h->cfg.channels, h->num_cus, split_hint, (hipStream_t)stream);
-        if (e == hipErrorNotSupported) return fail(SMOE_ERR_UNSUPPORTED, "smoe_shared_render: more than 2^30 samples per batch");
-        if (e != hipSuccess) return fail_hip(e, "smoe_shared_render launch");
-    }
-    return SMOE_OK;
+    return decoder_launched(fn, smoe::launch_shared_render(a, D, h->cfg.channels, h->num_cus, split_hint, (hipStream_t)stream),
+                            "more than 2^30 samples per batch");
 }
 
 // gather: sum the batches' rows into the gradient buffer right away (what smoe_shared_grad_buffer hands out for the

@@ -158,6 +158,14 @@ struct RenderBlendArgs {
     int off_w;                                  // float offset of the neighbour-weight tables in the dynamic LDS (launcher)
 };
 
+// What the launcher of a block decoder derives from checked arguments, next to the geometry fields of RenderArgs (and off_w
+// of RenderBlendArgs) it fills: a pure host computation (render_layout / render_blend_layout), also run without a device
+struct RenderLayout {
+    int hl;                   // the hoisting level the launch runs with
+    size_t lds_bytes;         // dynamic LDS of a workgroup
+    long long workgroups;
+};
+
 // The graph a fit or evaluation launch runs; with the tiling (Variant) it names one kernel instantiation
 // (resolve_fit / resolve_fwd in smoe_block.hip.h).
 struct Graph {
@@ -189,6 +197,9 @@ struct Variant {
     hipError_t (*render)(const RenderArgs&, int hl, int lanes, hipStream_t);
     // seam-free decoder (smoe_render_blend.hip.h), same conventions
     hipError_t (*render_blend)(const RenderBlendArgs&, int hl, int lanes, hipStream_t);
+    // the launch geometry of the two decoders alone: what render / render_blend compute before they launch, for the same arguments
+    hipError_t (*render_layout)(RenderArgs&, int hl, int lanes, RenderLayout&);
+    hipError_t (*render_blend_layout)(RenderBlendArgs&, int hl, int lanes, RenderLayout&);
 };
 
 // ---- shared-kernel image mode (smoe_shared.hip) ----------------------------------------------

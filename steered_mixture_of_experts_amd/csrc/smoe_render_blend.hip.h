@@ -121,63 +121,30 @@ __global__ void __launch_bounds__(RENDER_THREADS) render_blend_kernel(RenderBlen
     const RenderArgs& a = b.r;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x;
-    const int ML = a.m[D - 1];
-    const int MO = (D == 3) ? a.m[0] * a.m[1] : a.m[0];
-    const int GL = a.grid[D - 1];
-    const int line = a.line0 + (int)(blockIdx.x / (unsigned)a.chunks);
-    const int gl0 = (int)(blockIdx.x % (unsigned)a.chunks) * a.NB;
-    const int g0 = (D == 3) ? line / a.grid[1] : line;
-    const int g1 = (D == 3) ? line - g0 * a.grid[1] : 0;
-    const long long id0 = (long long)line * GL + gl0;
-    const int lb_lo = (int)max(0LL, (long long)a.first - id0);
-    const int lb_hi = (int)min((long long)min(a.NB, GL - gl0), (long long)a.first + a.nb - id0);
-    if (lb_lo >= lb_hi) return;
+    RenderFrame<D> f;
+    if (!f.place(a)) return;
+    const int g0 = f.g0, g1 = f.g1, gl0 = f.gl0;
 
     // LDS: axis tables | neighbour-weight tables | block records | staging (two buffers of values + kernel ids)
     float* s_ax = lds;
     float* s_w = lds + b.off_w;
     float* s_rec = lds + a.off_par;
-    uint32_t* s_stage = reinterpret_cast<uint32_t*>(lds + a.off_stage);
-    const int per = a.RP * a.NB * a.CL;
-    const int stg = per * (C + 1);
-    int ax_off[D];
-    {
-        int o = 0;
-#pragma unroll
-        for (int l = 0; l < D; ++l) { ax_off[l] = o; o += a.m[l]; }
-#pragma unroll
-        for (int l = 0; l < D; ++l)
-            for (int i = tid; i < a.m[l]; i += RENDER_THREADS) {
-                const float u = a.ax[l][i];
-                float w = 0.0f;
-                if (b.band[l] > 0.0f) {
-                    const float hi = fminf(fmaxf(0.5f * (1.0f + (u - b.s1[l]) / b.band[l]), 0.0f), 1.0f);
-                    const float lo = fminf(fmaxf(0.5f * (1.0f + (b.s0[l] - u) / b.band[l]), 0.0f), 1.0f);
-                    w = (hi > 0.0f) ? hi : -lo;
-                }
-                s_ax[ax_off[l] + i] = u;
-                s_w[ax_off[l] + i] = w;
-            }
-    }
+    render_load_axes<D>(a, f, [&](int l, int slot, float u) {
+        float w = 0.0f;
+        if (b.band[l] > 0.0f) {
+            const float hi = fminf(fmaxf(0.5f * (1.0f + (u - b.s1[l]) / b.band[l]), 0.0f), 1.0f);
+            const float lo = fminf(fmaxf(0.5f * (1.0f + (b.s0[l] - u) / b.band[l]), 0.0f), 1.0f);
+            w = (hi > 0.0f) ? hi : -lo;
+        }
+        s_ax[slot] = u;
+        s_w[slot] = w;
+    });
     const int ni = a.NB + 2;
     const int nrec = Rc::OUTER * ni;
-    for (int i = tid; i < nrec * Lt::LP_STRIDE; i += RENDER_THREADS) {
-        const int rec = i / Lt::LP_STRIDE;
-        const int j = i - rec * Lt::LP_STRIDE;
-        const long long id = record_block<D>(a, rec, ni, g0, g1, gl0);
-        float v = 0.0f;
-        if (id >= 0) {
-            if (j < Lt::NPAR) {
-                int tensor, kern;
-                long off;
-                decode_slot<D, C, K>(j, (int)id, tensor, off, kern);
-                v = pick(a.p, tensor)[off];
-            } else if (j < Lt::LP_ACT + K) {
-                v = (a.active == nullptr || ((a.active[id] >> (j - Lt::LP_ACT)) & 1u)) ? 1.0f : 0.0f;
-            }
-        }
-        s_rec[rec * Rc::STRIDE + j] = v;
-    }
+    render_load_images<D, C, K, Rc::STRIDE>(a, s_rec, nrec, [&](int rec, long long& id) {
+        id = record_block<D>(a, rec, ni, g0, g1, gl0);
+        return id >= 0;
+    });
     __syncthreads();
     // one lane per record: what every lane of render_kernel does for its block, kept for all of them
     for (int rec = tid; rec < nrec; rec += RENDER_THREADS) {
@@ -192,14 +159,8 @@ __global__ void __launch_bounds__(RENDER_THREADS) render_blend_kernel(RenderBlen
     }
     __syncthreads();
 
-    const int lpb = a.CL * a.RP;
-    const int lb = tid / lpb;
-    const int wi = tid - lb * lpb;
-    const int ph = wi / a.CL;
-    const int jl0 = wi - ph * a.CL;
-    const bool lane_ok = lb >= lb_lo && lb < lb_hi;
-    const int lbc = lane_ok ? lb : lb_lo;
-    const int own_rec = Rc::CENTRE * ni + lbc + 1;
+    const RenderLane n = render_lane<D>(a, f);
+    const int own_rec = Rc::CENTRE * ni + n.lbc + 1;
     const int rec_step0 = (D == 3) ? 3 * ni : ni;          // record index step per block along axis 0 (axis 1 of three: ni)
 
     BlockRegs<D, C, K> R;
@@ -208,60 +169,40 @@ __global__ void __launch_bounds__(RENDER_THREADS) render_blend_kernel(RenderBlen
     float t0[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) t0[c] = 0.0f;
-    const int npass = (ML + a.CL - 1) / a.CL;
-    const int nit = (MO + a.RP - 1) / a.RP;
-    const int ve_img = a.vec_img ? ((a.fmt == SMOE_IMAGE_U8) ? 16 : 4) : 1;
-    const int ve_arg = a.vec_arg ? 16 : 1;
-    int buf = 0;
-    for (int pass = 0; pass < npass; ++pass) {
-        const int jl = jl0 + pass * a.CL;
-        const bool col_ok = lane_ok && jl < ML;
+    RenderWalk<D, C> w;
+    w.begin(a, f, lds);
+    for (int pass = 0; pass < w.npass; ++pass) {
         float xc[D];
-#pragma unroll
-        for (int l = 0; l < D; ++l) xc[l] = 0.0f;
-        xc[D - 1] = s_ax[ax_off[D - 1] + min(jl, ML - 1)];
+        int cur1;
+        const int jl = render_begin_pass<D, C, K, HL, IC>(a, f, n, s_ax, pass, R, xc, cur1);
+        const bool col_ok = n.ok && jl < f.ML;
         float wn[D];                                       // weight of the neighbour per axis, sd: its side
         int sd[D];
         {
-            const float w = s_w[ax_off[D - 1] + min(jl, ML - 1)];
-            sd[D - 1] = (w > 0.0f) ? 1 : -1;
-            const int gn = gl0 + lbc + sd[D - 1];
-            wn[D - 1] = (gn >= 0 && gn < GL) ? fabsf(w) : 0.0f;
+            const float sw = s_w[f.ax_off[D - 1] + min(jl, f.ML - 1)];
+            sd[D - 1] = (sw > 0.0f) ? 1 : -1;
+            const int gn = gl0 + n.lbc + sd[D - 1];
+            wn[D - 1] = (gn >= 0 && gn < f.GL) ? fabsf(sw) : 0.0f;
         }
-        int cur1 = -1;
-        if (HL == 1) hoist_const<D, C, K, HL, IC>(R, xc);
-        for (int it = 0; it < nit; ++it) {
-            const int o = it * a.RP + ph;
-            uint32_t* sv = s_stage + buf * stg;
-            uint32_t* sa = sv + per * C;
-            if (col_ok && o < MO) {
+        for (int it = 0; it < w.nit; ++it) {
+            const int o = it * a.RP + n.ph;
+            if (col_ok && o < f.MO) {
                 float x[D];
-                x[D - 1] = xc[D - 1];
+                int jo[D - 1];
+                render_fetch_coords<D, C, K, HL, IC>(a, f, s_ax, o, R, xc, cur1, x, jo);
                 if (D == 3) {
-                    const int j0 = o / a.m[1], j1 = o - j0 * a.m[1];
-                    x[0] = s_ax[j0];
-                    x[1] = s_ax[ax_off[1] + j1];
-                    if (HL == 2 && j1 != cur1) {
-                        xc[1] = x[1];
-                        hoist_const<D, C, K, HL, IC>(R, xc);
-                        cur1 = j1;
-                    }
-                    const float w0 = s_w[j0], w1 = s_w[ax_off[1] + j1];
+                    const float w0 = s_w[jo[0]], w1 = s_w[f.ax_off[1] + jo[D - 2]];
                     sd[0] = (w0 > 0.0f) ? 1 : -1;
                     sd[1] = (w1 > 0.0f) ? 1 : -1;
                     wn[0] = (g0 + sd[0] >= 0 && g0 + sd[0] < a.grid[0]) ? fabsf(w0) : 0.0f;
                     wn[1] = (g1 + sd[1] >= 0 && g1 + sd[1] < a.grid[1]) ? fabsf(w1) : 0.0f;
                 } else {
-                    x[0] = s_ax[o];
-                    const float w0 = s_w[o];
+                    const float w0 = s_w[jo[0]];
                     sd[0] = (w0 > 0.0f) ? 1 : -1;
                     wn[0] = (g0 + sd[0] >= 0 && g0 + sd[0] < a.grid[0]) ? fabsf(w0) : 0.0f;
                 }
-                float acc[Lt::NSLOT];
-#pragma unroll
-                for (int j = 0; j < Lt::NSLOT; ++j) acc[j] = 0.0f;
                 PixelOut<D, C, K> po;
-                pixel<D, C, K, false, HL, false, IC, false>(R, a.kc, x, t0, 1.0f, acc, po);
+                render_eval<D, C, K, HL, IC>(a, R, x, po);
                 bool band = false;
 #pragma unroll
                 for (int l = 0; l < D; ++l) band = band || (wn[l] > 0.0f);
@@ -315,86 +256,32 @@ __global__ void __launch_bounds__(RENDER_THREADS) render_blend_kernel(RenderBlen
                         }
                     }
                 }
-                const int si = (ph * a.NB + lb) * a.CL + jl0;
-                if (a.fmt == SMOE_IMAGE_U8) {
-#pragma unroll
-                    for (int c = 0; c < C; ++c) sv[si * C + c] = (uint32_t)po.kq[c];
-                } else {
-#pragma unroll
-                    for (int c = 0; c < C; ++c) sv[si * C + c] = __float_as_uint(po.q[c]);
-                }
-                if (a.argmax != nullptr) {
-                    float best = 0.0f;
-                    uint32_t arg = 255u;
-#pragma unroll
-                    for (int k = 0; k < K; ++k)
-                        if (po.wt[k] > best) { best = po.wt[k]; arg = (uint32_t)k; }
-                    sa[si] = arg;
-                }
+                render_stage_sample<D, C, K>(a, n, w, po);
             }
-            __syncthreads();
-            if (a.fmt == SMOE_IMAGE_U8) render_flush<D, true>(a, sv, a.image, C, ve_img, it, pass, lb_lo, lb_hi, g0, g1, gl0);
-            else render_flush<D, false>(a, sv, a.image, C, ve_img, it, pass, lb_lo, lb_hi, g0, g1, gl0);
-            if (a.argmax != nullptr) render_flush<D, true>(a, sa, a.argmax, 1, ve_arg, it, pass, lb_lo, lb_hi, g0, g1, gl0);
-            buf ^= 1;
+            render_flush_step<D, C>(a, f, w, it, pass);
         }
     }
 }
 
+template <int D, int C, int K>
+struct RenderBlendFamily {
+    using Rc = BlendRec<D, C, K>;
+    template <int HL, bool QUANT, bool IC>
+    static auto kernel() -> void (*)(RenderBlendArgs) { return &render_blend_kernel<D, C, K, HL, QUANT, IC>; }
+    // the records of 3^(d-1) x (NB + 2) blocks, at most 48 KB of them; the coordinate and the weight table of every axis
+    static constexpr RenderRecords records() { return {Rc::STRIDE, Rc::OUTER, 2, 2, 48u * 1024u}; }
+};
+
+template <int D, int C, int K, bool FULL>
+hipError_t render_blend_layout(RenderBlendArgs& b, int hl, int lanes, RenderLayout& g) {
+    return render_layout(D, C, FULL, RenderBlendFamily<D, C, K>::records(), b.r, &b.off_w, hl, lanes, g);
+}
+
+// (the own block's samples follow smoe_render's order of operations: the same hoisting clamps, the same geometry rules)
 template <int D, int C, int K, bool FULL>
 hipError_t launch_render_blend(const RenderBlendArgs& b0, int hl, int lanes, hipStream_t st) {
-    using Rc = BlendRec<D, C, K>;
     RenderBlendArgs b = b0;
-    RenderArgs& a = b.r;
-    const bool ic = a.kc.inverse_cov != 0;
-    const bool q = a.kc.qmode != 0;
-    if (q && !FULL) return hipErrorNotSupported;
-    if (hl > D - 1) hl = D - 1;
-    if (q && hl > 1) hl = 1;                               // as launch_render: the own block's samples follow smoe_render's order
-    void (*kern)(RenderBlendArgs) = nullptr;
-#define SMOE_BLEND_PICK(H)                                                                                                   \
-    do {                                                                                                                     \
-        if constexpr (FULL && (H) <= 1) {                                                                                    \
-            if (q) kern = ic ? render_blend_kernel<D, C, K, (H), true, true> : render_blend_kernel<D, C, K, (H), true, false>;   \
-        }                                                                                                                    \
-        if (!q) kern = ic ? render_blend_kernel<D, C, K, (H), false, true> : render_blend_kernel<D, C, K, (H), false, false>;    \
-    } while (0)
-    if (hl == 0) SMOE_BLEND_PICK(0);
-    if (hl == 1) SMOE_BLEND_PICK(1);
-    if constexpr (D == 3) {
-        if (hl == 2) SMOE_BLEND_PICK(2);
-    }
-#undef SMOE_BLEND_PICK
-    if (kern == nullptr) return hipErrorNotSupported;
-    render_geometry(D, a.m, a.grid[D - 1], lanes, hl, a);
-    // the records of 3^(d-1) x (NB + 2) blocks: fewer blocks per workgroup where they would take more than 48 KB, the lanes
-    // that frees go to further outer sample tuples (a sample's arithmetic does not depend on the geometry)
-    const int nb_plain = a.NB;
-    while (a.NB > 1 && sizeof(float) * (size_t)Rc::OUTER * (a.NB + 2) * Rc::STRIDE > 48u * 1024u) --a.NB;
-    if (a.NB < nb_plain) {
-        const long MO = (D == 3) ? (long)a.m[0] * a.m[1] : a.m[0];
-        long rp = RENDER_THREADS / (a.CL * a.NB);
-        if (rp > MO) rp = MO;
-        if (rp > a.RP) a.RP = (int)rp;
-    }
-    a.chunks = (a.grid[D - 1] + a.NB - 1) / a.NB;
-    long msum = 0;
-    for (int l = 0; l < D; ++l) msum += a.m[l];
-    if (msum > 16384) return hipErrorNotSupported;         // the coordinate and the weight tables live in LDS (smoe_render: 32768)
-    b.off_w = round_up((int)msum, 4);
-    a.off_par = 2 * b.off_w;
-    a.off_stage = a.off_par + Rc::OUTER * (a.NB + 2) * Rc::STRIDE;
-    const size_t shm = sizeof(float) * ((size_t)a.off_stage + 2u * (size_t)a.RP * a.NB * a.CL * (C + 1));
-    if (shm > 160u * 1024u) return hipErrorNotSupported;
-    const long long GL = a.grid[D - 1];
-    const long long line_lo = a.first / GL, line_hi = ((long long)a.first + a.nb - 1) / GL;
-    a.line0 = (int)line_lo;
-    const long long wgs = (line_hi - line_lo + 1) * a.chunks;
-    if (wgs > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipError_t e = allow_lds(reinterpret_cast<const void*>(kern), shm);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(RENDER_THREADS), shm, st, b);
-    return hipGetLastError();
+    return launch_block_decoder<RenderBlendFamily<D, C, K>, D, FULL>(b, b.r, hl, lanes, st, &render_blend_layout<D, C, K, FULL>);
 }
 
 }  // namespace smoe

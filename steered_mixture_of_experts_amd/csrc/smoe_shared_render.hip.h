@@ -20,7 +20,7 @@
 //
 // Stores.  A tile is a handful of runs along the innermost image axis (whole rows of the batch, a ragged first / last one).
 // The values are turned through LDS and leave as 16-byte non-temporal stores on 16-byte boundaries of the IMAGE when its
-// base is aligned, element-wise at the runs' heads / tails (render_store_piece of smoe_render.hip.h); uint8 output and
+// base is aligned, element-wise at the runs' heads / tails (render_store_run of smoe_render.hip.h); uint8 output and
 // the kernel-id plane take the same path.
 //
 // ids: first maximum among the kernels with influence on the sample, -1 where none has.  smoe_shared_forward patches such
@@ -61,12 +61,8 @@ __device__ __forceinline__ void shared_render_flush(const SharedRenderArgs& a, c
         } else {
             row = org[0] + o;
         }
-        const long long e0 = (row * EL + org[D - 1] + ja) * cps, e1 = e0 + (long long)(jb - ja) * cps;
-        const long long c0 = ((e0 >> vs) + ch) << vs;            // (a 64-bit division by ve otherwise)
-        if (c0 >= e1) continue;
-        const long long lo = (c0 > e0) ? c0 : e0;
-        const long long hi = (c0 + ve < e1) ? c0 + ve : e1;
-        render_store_piece<U8>(st, img, lo, hi, e0, (o * ML + ja - n0) * cps, ve);
+        const long long e0 = (row * EL + org[D - 1] + ja) * cps;
+        render_store_run<U8>(st, img, e0, e0 + (long long)(jb - ja) * cps, (o * ML + ja - n0) * cps, vs, ch);
     }
 }
 
@@ -183,8 +179,7 @@ __global__ void __launch_bounds__(SH_THREADS) shared_render_kernel(SharedRenderA
         int arg[SR_PXL];
 #pragma unroll
         for (int p = 0; p < SR_PXL; ++p) {
-            best[p] = 0.0f;
-            arg[p] = -1;
+            first_max_init(best[p], arg[p], -1);
 #pragma unroll
             for (int c = 0; c < C; ++c) y[p][c] = 0.0f;
         }
@@ -200,7 +195,7 @@ __global__ void __launch_bounds__(SH_THREADS) shared_render_kernel(SharedRenderA
                     float z[D];
                     const float w = shared_gate<D, C, IC>(r, x[p], z) * inv[p];
                     const float wt = (pv[p] && w > a.kc.tau) ? w : 0.0f;
-                    if (wt > best[p]) { best[p] = wt; arg[p] = kid; }
+                    first_max_take(best[p], arg[p], wt, kid);
 #pragma unroll
                     for (int c = 0; c < C; ++c) {
                         float ee = r[L::O_NU + c];
@@ -241,11 +236,7 @@ size_t shared_render_lds_bytes(int D, int C, int K) {
 template <int D, int C>
 static hipError_t launch_shared_render_dc(const SharedRenderArgs& a, hipStream_t st) {
     auto kern = (a.kc.inverse_cov != 0) ? shared_render_kernel<D, C, true> : shared_render_kernel<D, C, false>;
-    const size_t shm = shared_render_lds_bytes(D, C, a.K);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((long long)a.nb * a.split)), dim3(SH_THREADS), shm, st, a);
-    return hipGetLastError();
+    return launch_decoder(kern, (long long)a.nb * a.split, SH_THREADS, shared_render_lds_bytes(D, C, a.K), a, st);
 }
 
 // num_cus: compute units of the device; split_hint > 0 forces the workgroups per batch (test / tuning hook), otherwise

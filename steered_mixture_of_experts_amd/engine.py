@@ -173,23 +173,38 @@ class _Engine:
         return AdamState(params, self.cfg.beta1, self.cfg.beta2)
 
     # -- render plumbing -----------------------------------------------------------
-    @staticmethod
-    def _check_render_dtype(dtype):
+    def _check_render_arity(self, who, dtype, axes, others, needs):
+        """The pixel type, and one entry per axis in ``axes`` and in each of ``others``.  ``who`` / ``needs``: the method's
+        name and the wording of the arity in its message."""
+        d = self.cfg.dim
         if dtype not in (torch.float32, torch.uint8):
             raise ValueError("render: dtype must be torch.float32 or torch.uint8")
+        if len(axes) != d or any(len(v) != d for v in others):
+            raise ValueError(f"{who}: {needs} need {d} entries")
 
-    def _is_axis_table(self, t) -> bool:
-        return t.dim() == 1 and t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device
+    def _check_axis_tables(self, who, axes, lengths=None):
+        """Every axis table a float32 vector on the device, with ``lengths[l]`` entries (default: at least one)."""
+        for l, t in enumerate(axes):
+            if t.dim() != 1 or t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device \
+                    or (t.numel() < 1 if lengths is None else t.numel() != lengths[l]):
+                raise ValueError(f"{who}: every axis table must be a contiguous 1-d float32 tensor on {self.device}"
+                                 + ("" if lengths is None else f" with grid * samples entries ({lengths})"))
 
-    def _render_out(self, out, extent, dtype, everything: bool):
-        """The image ``[*extent, C]`` to render into: ``out`` checked, or a new one (zero-filled unless the call renders
-        ``everything``), and the pixel format constant of ``dtype``."""
+    def _render_planes(self, out, extent, dtype, everything: bool, want_argmax: bool, none, id_dtype):
+        """The image ``[*extent, C]`` to render into -- ``out`` checked, or a new one (zero-filled unless the call renders
+        ``everything``) --, the pixel format constant of ``dtype``, and the kernel-id map ``[*extent]`` filled with
+        ``none`` (or None)."""
         shape = tuple(extent) + (self.cfg.channels,)
         if out is None:
             out = (torch.empty if everything else torch.zeros)(shape, dtype=dtype, device=self.device)
         elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or out.device != self.device:
             raise ValueError(f"render: out must be a contiguous {dtype} tensor {shape} on {self.device}")
-        return out, (_lib.SMOE_IMAGE_U8 if dtype == torch.uint8 else _lib.SMOE_IMAGE_F32)
+        am = torch.full(tuple(extent), none, dtype=id_dtype, device=self.device) if want_argmax else None
+        return out, (_lib.SMOE_IMAGE_U8 if dtype == torch.uint8 else _lib.SMOE_IMAGE_F32), am
+
+    @staticmethod
+    def _axis_slots(axes):
+        return _slots(C.c_void_p, [t.data_ptr() for t in axes], None)
 
 
 class BlockEngine(_Engine):
@@ -290,6 +305,36 @@ class BlockEngine(_Engine):
                                          int(update_active), self._stream()))
         return out
 
+    def _render(self, who, entry, params, active, covered, axes, grid, extent, first_block, B, out, dtype, want_argmax,
+                blend=None):
+        """``render`` and ``render_blend``: ``who`` names the method in the messages, ``entry`` is its C entry point.
+        ``covered``: the blocks ``params`` and ``active`` hold; ``B``: the blocks to render; ``blend``: render_blend's."""
+        d = self.cfg.dim
+        self._check_params(params, covered)
+        self._check_render_arity(who, dtype, axes, (grid, extent), "axes, grid and extent")
+        self._check_axis_tables(who, axes)
+        if blend is not None:
+            bl = [float(v) for v in np.atleast_1d(blend)]
+            bl = bl * d if len(bl) == 1 else bl
+            if len(bl) != d:
+                raise ValueError(f"{who}: blend needs one value or {d}")
+        grid = [int(g) for g in grid]
+        extent = [int(e) for e in extent]
+        total = 1
+        for g in grid:
+            total *= g
+        if active is not None and (tuple(active.shape) != (covered,) or active.dtype != torch.int32 or active.device != self.device):
+            raise ValueError(f"{who}: active must be int32 [{covered}] on {self.device}")
+        out, fmt, am = self._render_planes(out, extent, dtype, first_block == 0 and B == total, want_argmax, 255, torch.uint8)
+        if B > 0:
+            cp = self._cparams(params)
+            args = [self._h, int(first_block), B, C.byref(cp), _ptr(active), self._axis_slots(axes),
+                    _slots(C.c_int32, [int(t.numel()) for t in axes], 1), _slots(C.c_int32, grid, 1), _slots(C.c_int64, extent, 1)]
+            if blend is not None:
+                args.append(_slots(C.c_float, bl, 0.0))
+            _lib.check(entry(*args, _ptr(out), fmt, _ptr(am), self._stream()))
+        return (out, am) if want_argmax else out
+
     def render(self, params, active, axes, grid, extent, first_block=0, out=None, dtype=torch.float32,
                want_argmax=False):
         """Decode: evaluate the blocks ``[first_block, first_block + B)`` of an image-wide block ``grid`` on the separable
@@ -298,32 +343,9 @@ class BlockEngine(_Engine):
         full-size image to render into (only the positions of the rendered blocks are written); otherwise a new one,
         zero-filled where this call renders only a part.  Returns the image, with ``want_argmax`` also the uint8 kernel
         map ``[*extent]`` (255: no kernel has influence; 255 as well where no block was rendered)."""
-        d = self.cfg.dim
         B = int(params["pis"].shape[0])
-        self._check_params(params, B)
-        self._check_render_dtype(dtype)
-        if len(axes) != d or len(grid) != d or len(extent) != d:
-            raise ValueError(f"render: axes, grid and extent need {d} entries")
-        for t in axes:
-            if t.numel() < 1 or not self._is_axis_table(t):
-                raise ValueError(f"render: every axis table must be a contiguous 1-d float32 tensor on {self.device}")
-        grid = [int(g) for g in grid]
-        extent = [int(e) for e in extent]
-        total = 1
-        for g in grid:
-            total *= g
-        if active is not None and (tuple(active.shape) != (B,) or active.dtype != torch.int32 or active.device != self.device):
-            raise ValueError(f"render: active must be int32 [{B}] on {self.device}")
-        out, fmt = self._render_out(out, extent, dtype, everything=(first_block == 0 and B == total))
-        am = torch.full(tuple(extent), 255, dtype=torch.uint8, device=self.device) if want_argmax else None
-        if B > 0:
-            cp = self._cparams(params)
-            tabs = _slots(C.c_void_p, [t.data_ptr() for t in axes], None)
-            m3 = _slots(C.c_int32, [int(t.numel()) for t in axes], 1)
-            _lib.check(self.lib.smoe_render(self._h, int(first_block), B, C.byref(cp), _ptr(active), tabs, m3,
-                                            _slots(C.c_int32, grid, 1), _slots(C.c_int64, extent, 1),
-                                            _ptr(out), fmt, _ptr(am), self._stream()))
-        return (out, am) if want_argmax else out
+        return self._render("render", self.lib.smoe_render, params, active, B, axes, grid, extent, first_block, B, out, dtype,
+                            want_argmax)
 
     def render_blend(self, params, active, axes, grid, extent, blend, first_block=0, num_blocks=None, out=None,
                      dtype=torch.float32, want_argmax=False, center_grid=None):
@@ -333,43 +355,22 @@ class BlockEngine(_Engine):
         of the rendered range ``[first_block, first_block + num_blocks)`` (default: up to the last block) are read --
         and so does ``center_grid`` [prod(grid), K, d], the image-wide kernel grid of a use_diff_center model whose
         engine holds a shard's grid (it is put back afterwards).  Returns what ``render`` returns."""
-        d = self.cfg.dim
         total = 1
         for g in grid:
             total *= int(g)
-        self._check_params(params, total)
-        self._check_render_dtype(dtype)
-        if len(axes) != d or len(grid) != d or len(extent) != d:
-            raise ValueError(f"render_blend: axes, grid and extent need {d} entries")
-        for t in axes:
-            if t.numel() < 1 or not self._is_axis_table(t):
-                raise ValueError(f"render_blend: every axis table must be a contiguous 1-d float32 tensor on {self.device}")
-        bl = [float(v) for v in np.atleast_1d(blend)]
-        bl = bl * d if len(bl) == 1 else bl
-        if len(bl) != d:
-            raise ValueError(f"render_blend: blend needs one value or {d}")
-        grid = [int(g) for g in grid]
-        extent = [int(e) for e in extent]
         B = total - int(first_block) if num_blocks is None else int(num_blocks)
-        if active is not None and (tuple(active.shape) != (total,) or active.dtype != torch.int32 or active.device != self.device):
-            raise ValueError(f"render_blend: active must be int32 [{total}] on {self.device}")
-        out, fmt = self._render_out(out, extent, dtype, everything=(first_block == 0 and B == total))
-        am = torch.full(tuple(extent), 255, dtype=torch.uint8, device=self.device) if want_argmax else None
-        if B > 0:
-            cp = self._cparams(params)
-            tabs = _slots(C.c_void_p, [t.data_ptr() for t in axes], None)
-            m3 = _slots(C.c_int32, [int(t.numel()) for t in axes], 1)
-            held = getattr(self, "_center_grid", None)
+        held = getattr(self, "_center_grid", None)
+
+        def entry(*args):                                    # the image-wide centre grid around the launch alone
             if center_grid is not None:
                 self.set_center_grid(center_grid)
             try:
-                _lib.check(self.lib.smoe_render_blend(self._h, int(first_block), B, C.byref(cp), _ptr(active), tabs, m3,
-                                                      _slots(C.c_int32, grid, 1), _slots(C.c_int64, extent, 1),
-                                                      _slots(C.c_float, bl, 0.0), _ptr(out), fmt, _ptr(am), self._stream()))
+                return self.lib.smoe_render_blend(*args)
             finally:
                 if center_grid is not None:
                     self.set_center_grid(held)
-        return (out, am) if want_argmax else out
+        return self._render("render_blend", entry, params, active, total, axes, grid, extent, first_block, B, out, dtype,
+                            want_argmax, blend)
 
     def fit(self, target, params, state: AdamState, active, n_iters: int, loss_w=None, diverged=None,
             loss0=None, loss_out=None, sse_out=None, loss_w_is_sample=False):
@@ -506,19 +507,13 @@ class SharedEngine(_Engine):
         rendered batches are written); otherwise a new one, zero-filled where this call renders only a part.  Returns the
         image, with ``want_argmax`` also the int32 map ``[*E]`` of global kernel ids (-1: no kernel has influence on the
         sample; -1 as well where no batch was rendered)."""
-        d = self.cfg.dim
-        self._check_render_dtype(dtype)
-        if len(axes) != d or len(samples) != d:
-            raise ValueError(f"render: axes and samples need {d} entries")
+        self._check_render_arity("render", dtype, axes, (samples,), "axes and samples")
         samples = [int(m) for m in samples]
         if min(samples) < 1:
             raise ValueError("render: at least one sample per batch and axis")
         grid = [int(s) // int(b) for s, b in zip(self.cfg.image_shape, self.cfg.batch_shape)]
         extent = [g * m for g, m in zip(grid, samples)]
-        for t, e in zip(axes, extent):
-            if not self._is_axis_table(t) or t.numel() != e:
-                raise ValueError(f"render: every axis table must be a contiguous 1-d float32 tensor on {self.device} with "
-                                 f"grid * samples entries ({extent})")
+        self._check_axis_tables("render", axes, extent)
         if lists is not None:
             nb = int(lists.shape[0])
             if (tuple(lists.shape) != (nb, self.list_words) or lists.dtype != torch.int32 or not lists.is_contiguous()
@@ -528,12 +523,10 @@ class SharedEngine(_Engine):
             nb = self.num_batches - int(first_batch) if num_batches is None else int(num_batches)
         if first_batch < 0 or nb < 0 or first_batch + nb > self.num_batches:
             raise ValueError("render: batch range out of bounds")
-        out, fmt = self._render_out(out, extent, dtype, everything=(nb == self.num_batches))
-        am = torch.full(tuple(extent), -1, dtype=torch.int32, device=self.device) if want_argmax else None
+        out, fmt, am = self._render_planes(out, extent, dtype, nb == self.num_batches, want_argmax, -1, torch.int32)
         if nb > 0:
             cp = self._cparams(params)
-            tabs = _slots(C.c_void_p, [t.data_ptr() for t in axes], None)
-            _lib.check(self.lib.smoe_shared_render(self._h, int(first_batch), nb, C.byref(cp), _ptr(lists), tabs,
+            _lib.check(self.lib.smoe_shared_render(self._h, int(first_batch), nb, C.byref(cp), _ptr(lists), self._axis_slots(axes),
                                                    _slots(C.c_int32, samples, 1), _ptr(out), fmt, _ptr(am), self._stream()))
         return (out, am) if want_argmax else out
 

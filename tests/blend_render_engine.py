@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from oracle import smoe_oracle as o
-from render_engine import NAMES, OracleRenderEngine, place_blocks
+from render_engine import NAMES, OracleRenderEngine, decoded, mask_of
 
 
 def axis_weights(n, tab, beta, T=np.float32):
@@ -107,30 +107,13 @@ def blend_reference(p, active, tabs, n, grid, blend, ocfg, dtype=np.float32):
 class OracleBlendEngine(OracleRenderEngine):
     def render_blend(self, params, active, axes, grid, extent, blend, first_block=0, num_blocks=None, out=None,
                      dtype=torch.float32, want_argmax=False, center_grid=None):
-        K, Cc = self.cfg.kernels, self.cfg.channels
         p = {k: params[k].numpy() for k in NAMES}
         B = p["pis"].shape[0]
         assert B == int(np.prod(grid)), "render_blend takes the parameters of all blocks"
         count = B - first_block if num_blocks is None else int(num_blocks)
-        if active is None:
-            mask = np.ones((B, K), dtype=bool)
-        else:
-            act = active.numpy().view(np.uint32)
-            mask = ((act[:, None] >> np.arange(K, dtype=np.uint32)[None, :]) & 1).astype(bool)
-        m = [int(a.numel()) for a in axes]
-        extent = [int(e) for e in extent]
-        img = np.zeros(tuple(extent) + (Cc,), dtype=np.float32) if out is None else out.numpy()
-        am = np.full(tuple(extent), 255, dtype=np.uint8)
-        if dtype == torch.uint8 and out is None:
-            img = img.astype(np.uint8)
+        f = None
         if count > 0:
-            r = blend_reference(p, mask, [a.numpy() for a in axes], list(self.cfg.block_shape), list(grid), blend, self.ocfg)
-            q = r["recon"].astype(np.float32)[first_block:first_block + count]
-            if dtype == torch.uint8:
-                q = np.rint(q * (2 ** self.cfg.precision - 1)).astype(np.uint8)
-            place_blocks(q, m, grid, extent, first_block, img)
-            wt = r["wt0"][first_block:first_block + count]
-            arg = np.where(wt.max(axis=1) > 0, np.argmax(wt, axis=1), 255).astype(np.uint8)
-            place_blocks(arg[..., None], m, grid, extent, first_block, am[..., None])
-        res = torch.from_numpy(img) if out is None else out
-        return (res, torch.from_numpy(am)) if want_argmax else res
+            r = blend_reference(p, mask_of(active, B, self.cfg.kernels), [a.numpy() for a in axes], list(self.cfg.block_shape),
+                                list(grid), blend, self.ocfg)
+            f = (r["recon"][first_block:first_block + count], r["wt0"][first_block:first_block + count])
+        return decoded(f, [int(a.numel()) for a in axes], grid, extent, first_block, self.cfg, out, dtype, 255, np.uint8, want_argmax)

@@ -18,6 +18,9 @@ static int g_checks = 0, g_fail = 0;
 // --dump: one line per (config, tiling, total_blocks, B, loss weights) of the matrix drive_handle walks, with the decisions of
 // the host layer for it; compared between two builds of the library (nothing is committed as a golden file)
 static bool g_dump = false;
+// --dump-render: one line per case of the matrix check_render_layouts walks, with the launch geometry of the two block
+// decoders for it; compared between two builds in the same way
+static bool g_dump_render = false;
 #define EXPECT(cond)                                                                   \
     do {                                                                               \
         ++g_checks;                                                                    \
@@ -301,8 +304,79 @@ static void check_shared() {
     EXPECT(smoe_shared_num_batches(nullptr) == SMOE_ERR_INVALID);
 }
 
+// The launch geometry of smoe_render / smoe_render_blend (render_layout, render_blend_layout of every variant): every triple
+// and tiling of smoe_variants.def, the sample grids of the GPU render suites, shards of 1 / 9 / 37 / 2040 blocks from the
+// middle of the block grid, blend off and on, every hoisting level, plain and fake-quantised graph.
+static void check_render_layouts() {
+    struct Grid { int d; int m[3]; int grid[3]; };
+    static const Grid grids[] = {
+        {2, {16, 16, 1}, {5, 8, 1}}, {2, {32, 32, 1}, {5, 8, 1}}, {2, {40, 24, 1}, {5, 8, 1}}, {2, {48, 80, 1}, {5, 8, 1}},
+        {2, {11, 16, 1}, {5, 8, 1}}, {2, {24, 20, 1}, {5, 8, 1}}, {2, {3, 300, 1}, {5, 8, 1}},
+        {2, {16, 16, 1}, {3, 4, 1}}, {2, {40, 24, 1}, {3, 4, 1}}, {2, {48, 80, 1}, {3, 4, 1}}, {2, {11, 16, 1}, {3, 4, 1}},
+        {2, {24, 20, 1}, {3, 4, 1}}, {2, {3, 300, 1}, {3, 4, 1}},
+        {3, {16, 16, 4}, {5, 4, 2}}, {3, {32, 32, 7}, {5, 4, 2}}, {3, {12, 10, 3}, {5, 4, 2}}, {3, {6, 5, 9}, {5, 4, 2}},
+        {3, {16, 16, 7}, {5, 4, 2}}, {3, {32, 32, 7}, {2, 3, 2}}, {3, {6, 5, 9}, {2, 3, 2}}, {3, {2, 2, 3}, {1, 1, 9}},
+    };
+    int n = 0, capped = 0;
+    const smoe::Variant* v = smoe::variants(&n);
+    for (int i = 0; i < n; ++i)
+        for (const Grid& gr : grids) {
+            if (gr.d != v[i].D) continue;
+            for (int count : {1, 9, 37, 2040})
+                for (int blend = 0; blend < 2; ++blend)
+                    for (int hl = 0; hl < 3; ++hl)
+                        for (int q = 0; q < 2; ++q) {
+                            smoe::RenderBlendArgs b;
+                            std::memset(&b, 0, sizeof b);
+                            smoe::RenderArgs& a = b.r;
+                            long long rest = 1, total = 1;
+                            for (int l = 0; l < 3; ++l) {
+                                a.m[l] = gr.m[l]; a.grid[l] = gr.grid[l];
+                                if (l > 0) rest *= gr.grid[l];
+                            }
+                            if ((long long)a.grid[0] * rest < count) a.grid[0] = (int)((count + rest - 1) / rest);   // room for the shard
+                            for (int l = 0; l < 3; ++l) { a.ext[l] = (long long)a.grid[l] * a.m[l]; total *= a.grid[l]; }
+                            a.first = (int)((total - count) / 2); a.nb = count;
+                            a.kc.qmode = q ? 2 : 0;
+                            smoe::RenderLayout g;
+                            std::memset(&g, 0, sizeof g);
+                            const hipError_t e = blend ? v[i].render_blend_layout(b, hl, v[i].G, g) : v[i].render_layout(a, hl, v[i].G, g);
+                            EXPECT(e == hipSuccess || e == hipErrorNotSupported);
+                            if (e == hipSuccess) {
+                                EXPECT(g.hl >= 0 && g.hl <= hl && g.hl < v[i].D && (!q || g.hl <= 1));
+                                EXPECT(a.NB >= 1 && a.CL >= 1 && a.RP >= 1 && a.NB * a.CL * a.RP <= 256);
+                                EXPECT(a.chunks == (a.grid[v[i].D - 1] + a.NB - 1) / a.NB);
+                                EXPECT(g.lds_bytes <= 160u * 1024u && (g.lds_bytes & 3) == 0);
+                                EXPECT(sizeof(float) * ((size_t)a.off_stage + 2u * (size_t)a.RP * a.NB * a.CL * (v[i].C + 1)) == g.lds_bytes);
+                                EXPECT(a.off_par <= a.off_stage && (!blend || a.off_par == 2 * b.off_w));
+                                EXPECT(g.workgroups >= (count + a.NB - 1) / a.NB && a.line0 == a.first / a.grid[v[i].D - 1]);
+                                // the record-cap case of the GPU suite (samples 2 x 2 x 3 on a 1 x 1 x 9 grid): 9 x (NB + 2) records of 140 floats pass 48 KB above
+                                // NB = 7, where the plain decoder takes the nine blocks of the grid line at once
+                                if (v[i].C == 3 && v[i].K == 4 && gr.m[0] == 2 && gr.m[1] == 2 && gr.m[2] == 3 && gr.grid[2] == 9 && count == 9) {
+                                    EXPECT(a.NB == (blend ? 7 : 9));
+                                    ++capped;
+                                }
+                            }
+                            if (g_dump_render)
+                                std::printf("%s full%d | m %dx%dx%d grid %dx%dx%d first %d nb %d blend %d hl %d q %d | rc %d hl %d NB %d CL %d RP %d "
+                                            "chunks %d line0 %d off_w %d off_par %d off_stage %d lds %zu wgs %lld\n",
+                                            v[i].name, (int)v[i].full, a.m[0], a.m[1], a.m[2], a.grid[0], a.grid[1], a.grid[2], a.first, a.nb,
+                                            blend, hl, q, (int)e, g.hl, a.NB, a.CL, a.RP, a.chunks, a.line0, b.off_w, a.off_par, a.off_stage,
+                                            g.lds_bytes, g.workgroups);
+                        }
+        }
+    EXPECT(capped > 0);
+}
+
 int main(int argc, char** argv) {
     g_dump = argc > 1 && std::strcmp(argv[1], "--dump") == 0;
+    g_dump_render = argc > 1 && std::strcmp(argv[1], "--dump-render") == 0;
+    if (g_dump_render) {
+        check_render_layouts();
+        std::printf("hostcheck: %d checks, %d failed\n", g_checks, g_fail);
+        return g_fail ? 1 : 0;
+    }
+    if (!g_dump) check_render_layouts();                  // (--dump keeps to its own matrix: its output is compared between builds)
     check_create_refusals();
     check_variant_tables();
     check_block_handles();

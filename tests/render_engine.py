@@ -35,32 +35,43 @@ def place_blocks(vals, m, grid, extent, first_block, out):
     return out
 
 
+def mask_of(words, n, K):
+    """(n, K) bool from the bit words of ``n`` kernel lists ((n,) or (n, KW) int32 tensor; None: every kernel listed)."""
+    if words is None:
+        return np.ones((n, K), dtype=bool)
+    w = words.numpy().view(np.uint32).reshape(n, -1)
+    k = np.arange(K)
+    return ((w[:, k >> 5] >> (k & 31).astype(np.uint32)) & 1).astype(bool)
+
+
+def first_max_ids(wt, none, dtype):
+    """(n, K, M) masked gates -> (n, M) first maximum, ``none`` where no kernel has influence"""
+    return np.where(wt.max(axis=1) > 0, np.argmax(wt, axis=1), none).astype(dtype)
+
+
+def decoded(f, m, grid, extent, first, cfg, out, dtype, none, id_dtype, want_argmax):
+    """What a stand-in's ``render`` returns for the restatement's result ``f`` = (recon (n, M, C), wt (n, K, M)) of the blocks
+    from ``first`` on (None: nothing was rendered): the image -- ``out``, or a new one of zeros -- in ``dtype`` and the
+    kernel-id map, ``none`` where no kernel has influence or nothing was rendered."""
+    extent = [int(e) for e in extent]
+    img = out.numpy() if out is not None else np.zeros(tuple(extent) + (cfg.channels,), np.uint8 if dtype == torch.uint8 else np.float32)
+    am = np.full(tuple(extent), none, dtype=id_dtype)
+    if f is not None:
+        q = f[0].astype(np.float32)
+        if dtype == torch.uint8:
+            q = np.rint(q * (2 ** cfg.precision - 1)).astype(np.uint8)
+        place_blocks(q, m, grid, extent, first, img)
+        place_blocks(first_max_ids(f[1], none, id_dtype)[..., None], m, grid, extent, first, am[..., None])
+    res = torch.from_numpy(img) if out is None else out
+    return (res, torch.from_numpy(am)) if want_argmax else res
+
+
 class OracleRenderEngine(OracleEngine):
     def render(self, params, active, axes, grid, extent, first_block=0, out=None, dtype=torch.float32, want_argmax=False):
-        K, Cc = self.cfg.kernels, self.cfg.channels
         p = {k: params[k].numpy() for k in NAMES}
         B = p["pis"].shape[0]
-        if active is None:
-            mask = np.ones((B, K), dtype=bool)
-        else:
-            act = active.numpy().view(np.uint32)
-            mask = ((act[:, None] >> np.arange(K, dtype=np.uint32)[None, :]) & 1).astype(bool)
-        m = [int(a.numel()) for a in axes]
-        extent = [int(e) for e in extent]
-        img = np.zeros(tuple(extent) + (Cc,), dtype=np.float32) if out is None else out.numpy()
-        am = np.full(tuple(extent), 255, dtype=np.uint8)
+        f = None
         if B > 0:
-            f, _ = oracle_blocks(p, mask, [a.numpy() for a in axes], self.ocfg)
-            q = f["recon"].astype(np.float32)
-            if dtype == torch.uint8:
-                q = np.rint(q * (2 ** self.cfg.precision - 1)).astype(np.uint8)
-                if out is None:
-                    img = img.astype(np.uint8)
-            place_blocks(q, m, grid, extent, first_block, img)
-            wt = f["wt"]                                                       # (B, K, M)
-            arg = np.where(wt.max(axis=1) > 0, np.argmax(wt, axis=1), 255).astype(np.uint8)
-            place_blocks(arg[..., None], m, grid, extent, first_block, am[..., None])
-        elif dtype == torch.uint8 and out is None:
-            img = img.astype(np.uint8)
-        res = torch.from_numpy(img) if out is None else out
-        return (res, torch.from_numpy(am)) if want_argmax else res
+            r, _ = oracle_blocks(p, mask_of(active, B, self.cfg.kernels), [a.numpy() for a in axes], self.ocfg)
+            f = (r["recon"], r["wt"])
+        return decoded(f, [int(a.numel()) for a in axes], grid, extent, first_block, self.cfg, out, dtype, 255, np.uint8, want_argmax)

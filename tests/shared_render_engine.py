@@ -8,7 +8,7 @@ import torch
 
 from fake_engine import OracleSharedEngine
 from oracle import smoe_oracle as o
-from render_engine import place_blocks
+from render_engine import decoded, first_max_ids
 
 
 def batch_sample_coords(tabs, m, grid, first, nb):
@@ -33,33 +33,25 @@ def oracle_shared_batches(p, mask, tabs, m, grid, first, ocfg, dtype=np.float32)
 
 def ids_of(wt):
     """(nb, K, M) masked gates -> (nb, M) first maximum, -1 where no kernel has influence"""
-    return np.where(wt.max(axis=1) > 0, np.argmax(wt, axis=1), -1).astype(np.int32)
+    return first_max_ids(wt, -1, np.int32)
 
 
 class OracleSharedRenderEngine(OracleSharedEngine):
     def render(self, params, lists, axes, samples, first_batch=0, out=None, dtype=torch.float32, want_argmax=False,
                num_batches=None):
         cfg = self.cfg
-        K, Cc = cfg.kernels, cfg.channels
         m = [int(v) for v in samples]
         grid = [int(s) // int(b) for s, b in zip(cfg.image_shape, cfg.batch_shape)]
         extent = [g * v for g, v in zip(grid, m)]
         assert [int(a.numel()) for a in axes] == extent
         if lists is None:
             nb = self.num_batches - first_batch if num_batches is None else int(num_batches)
-            mask = np.ones((nb, K), dtype=bool)
+            mask = np.ones((nb, cfg.kernels), dtype=bool)
         else:
             nb = int(lists.shape[0])
             mask = self._mask(lists)
-        npdt = np.uint8 if dtype == torch.uint8 else np.float32
-        img = np.zeros(tuple(extent) + (Cc,), dtype=npdt) if out is None else out.numpy()
-        am = np.full(tuple(extent), -1, dtype=np.int32)
+        f = None
         if nb > 0:
-            f = oracle_shared_batches(self._p(params), mask, [a.numpy() for a in axes], m, grid, first_batch, self.ocfg)
-            q = f["recon"].astype(np.float32)
-            if dtype == torch.uint8:
-                q = np.rint(q * (2 ** cfg.precision - 1)).astype(np.uint8)
-            place_blocks(q, m, grid, extent, first_batch, img)
-            place_blocks(ids_of(f["wt"])[..., None], m, grid, extent, first_batch, am[..., None])
-        res = torch.from_numpy(img) if out is None else out
-        return (res, torch.from_numpy(am)) if want_argmax else res
+            r = oracle_shared_batches(self._p(params), mask, [a.numpy() for a in axes], m, grid, first_batch, self.ocfg)
+            f = (r["recon"], r["wt"])
+        return decoded(f, m, grid, extent, first_batch, cfg, out, dtype, -1, np.int32, want_argmax)

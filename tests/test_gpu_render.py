@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from oracle import smoe_oracle as o
+from render_cases import _axes, _bits, _dev_axes, _engine, _guarded, _image, _owned, _setup, _to_dev
 from render_engine import oracle_blocks, place_blocks
 from steered_mixture_of_experts_amd import blocks as blk
 from steered_mixture_of_experts_amd.blocks import synthetic_blocks
@@ -36,35 +37,6 @@ def _ids(cases):
     return ["x".join(map(str, c[0])) + f"-c{c[1]}" + "".join(f"-{x}" for x in c[4:] if isinstance(x, str)) for c in cases]
 
 
-def _engine(shape, C_, K, **kw):
-    from steered_mixture_of_experts_amd.engine import BlockEngine, EngineConfig
-    return BlockEngine(EngineConfig(block_shape=shape, channels=C_, kernels=K, **kw))
-
-
-def _to_dev(p):
-    return {k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).cuda() for k, v in p.items()}
-
-
-def _mask_to_bits(active):
-    K = active.shape[1]
-    return (active.astype(np.uint32) << np.arange(K, dtype=np.uint32)[None, :]).sum(axis=1).astype(np.uint32)
-
-
-def _setup(shape, C_, kpd, yuv, B, seed, **cfgkw):
-    """parameters as test_forward_parity draws them (perturbed initialisation)"""
-    K = int(np.prod(kpd))
-    b = synthetic_blocks(B, shape, C_, seed)
-    p = o.init_params(b, kpd)
-    rng = np.random.default_rng(seed + 1)
-    p["A_corr"] = (rng.normal(size=p["A_corr"].shape) * 1.5).astype(np.float32)
-    p["A_diagonal"] = (p["A_diagonal"] + rng.normal(size=p["A_diagonal"].shape)).astype(np.float32)
-    p["gamma_e"] = (rng.normal(size=p["gamma_e"].shape) * 0.1).astype(np.float32)
-    p["musX"] = (p["musX"] + rng.normal(size=p["musX"].shape) * 0.05).astype(np.float32)
-    p["pis"] = (p["pis"] * rng.uniform(0.5, 1.5, size=p["pis"].shape)).astype(np.float32)
-    cfg = o.OracleConfig(block_shape=shape, channels=C_, kernels=K, use_yuv=yuv, **cfgkw)
-    return cfg, p, b.reshape(B, -1, C_), K
-
-
 def _parity_inputs(shape, C_, kpd, yuv, **cfgkw):
     cfg, p, tgt, K = _setup(shape, C_, kpd, yuv, B37, 100 + len(shape) + C_, **cfgkw)
     active = np.random.default_rng(5).uniform(size=(B37, K)) < 0.85
@@ -75,21 +47,6 @@ def _parity_inputs(shape, C_, kpd, yuv, **cfgkw):
 
 def _grid_of(shape):
     return (5, 8) if len(shape) == 2 else (5, 4, 2)
-
-
-def _axes(n, m):
-    return [blk.render_axis(a, b) for a, b in zip(n, m)]
-
-
-def _dev_axes(tabs):
-    return [torch.from_numpy(np.ascontiguousarray(t)).cuda() for t in tabs]
-
-
-def _owned(m, grid, extent, first, count):
-    """bool [*extent]: positions of the blocks [first, first + count)"""
-    own = np.zeros(tuple(extent) + (1,), dtype=bool)
-    ones = np.ones((count, int(np.prod(m)), 1), dtype=bool)
-    return place_blocks(ones, m, grid, extent, first, own)[..., 0]
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -130,7 +87,7 @@ def test_identity_with_forward(case):
         gdev = torch.from_numpy(grid_mu).cuda()
         eng.set_center_grid(gdev)
     dp = _to_dev(p)
-    act = torch.from_numpy(_mask_to_bits(active).view(np.int32)).cuda()
+    act = _bits(active)
     T = torch.from_numpy(np.ascontiguousarray(np.transpose(tgt, (0, 2, 1)))).cuda()
     fw = eng.forward(T, dp, act, want_recon=True, want_argmax=True, update_active=False)
     grid = _grid_of(shape)
@@ -162,6 +119,7 @@ RESAMPLED = [
     ((7, 5), 1, [2, 2], False, (11, 16), {}),
     ((12, 10, 3), 3, [2, 2, 1], True, (6, 5, 9), {}),
     ((16, 16), 3, [2, 2], True, (40, 24), dict(train_inverse_cov=True)),
+    ((7, 5), 1, [2, 2], False, (3, 300), {}),    # 300 > 256 innermost samples: CL = 256, two passes, the second ragged
 ]
 
 
@@ -190,7 +148,7 @@ def test_parity_on_resampled_grids(case):
 
     eng = _engine(shape, C_, K, use_yuv=yuv, **kw)
     dp = _to_dev(p)
-    act = torch.from_numpy(_mask_to_bits(active).view(np.int32)).cuda()
+    act = _bits(active)
     grid = _grid_of(shape)
     extent = [g * mm for g, mm in zip(grid, m)]
     axes = _dev_axes(tabs)
@@ -218,12 +176,6 @@ def test_parity_on_resampled_grids(case):
 SENT = -7.0
 
 
-def _guarded(shape, dtype, fill, guard=64, shift=0):
-    n = int(np.prod(shape))
-    buf = torch.full((guard + n + guard + 8,), fill, dtype=dtype, device="cuda")
-    return buf, buf[guard + shift: guard + shift + n].view(*shape)
-
-
 @pytest.mark.parametrize("shape,C_,kpd,yuv,m", [((16, 16), 3, [2, 2], True, (16, 16)), ((16, 16), 1, [2, 2], False, (24, 20)),
                                                ((16, 16, 4), 3, [2, 2, 1], True, (16, 16, 7))],
                          ids=["16x16-c3", "16x16-c1-to-24x20", "16x16x4-c3-to-16x16x7"])
@@ -232,7 +184,7 @@ def test_shards_and_bounds(shape, C_, kpd, yuv, m):
     active[7] = False                                        # a block with no live kernel
     eng = _engine(shape, C_, K, use_yuv=yuv)
     dp = _to_dev(p)
-    act = torch.from_numpy(_mask_to_bits(active).view(np.int32)).cuda()
+    act = _bits(active)
     grid = _grid_of(shape)
     extent = [g * mm - max(1, mm // 3) for g, mm in zip(grid, m)]
     axes = _dev_axes(_axes(shape, m))
@@ -323,12 +275,6 @@ def test_shards_and_bounds(shape, C_, kpd, yuv, m):
 # ---------------------------------------------------------------------------------------------------------------
 # 8. the facade on the device
 # ---------------------------------------------------------------------------------------------------------------
-def _image(h, w, C_=1, seed=0):
-    gh, gw = -(-h // 16), -(-w // 16)
-    b = synthetic_blocks(gh * gw, (16, 16), C_, seed)
-    return blk.blocks_to_image(b, (gh * 16, gw * 16), (16, 16))[:h, :w]
-
-
 def test_facade_render_on_the_device():
     from steered_mixture_of_experts_amd.smoe import Adam, Smoe
     img = _image(40, 52, C_=3, seed=3)

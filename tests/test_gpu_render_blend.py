@@ -15,9 +15,9 @@ import pytest
 import torch
 
 from blend_render_engine import blend_reference
+from render_cases import _axes, _bits, _dev_axes, _engine, _guarded, _image, _owned, _setup, _to_dev
 from render_engine import place_blocks
 from steered_mixture_of_experts_amd import blocks as blk
-from test_gpu_render import _axes, _dev_axes, _engine, _guarded, _mask_to_bits, _owned, _setup, _to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -34,20 +34,26 @@ CASES = [
     ((16, 16), 1, [2, 2], (24, 20), 8, {}),                                  # the maximal band
     ((16, 16), 3, [2, 2], (40, 24), 2, dict(train_inverse_cov=True)),
     ((16, 16), 3, [2, 2], (40, 24), 2, MODE2),
+    # 300 > 256 innermost samples: CL = 256, two passes, the second ragged
+    ((7, 5), 1, [2, 2], (3, 300), 1, {}),
+    # nine blocks on a grid line: the 48 KB cap on the records lowers NB from 9 to 7 (9 x (NB + 2) records of 140 floats), so a
+    # workgroup boundary falls between blocks 6 and 7 and the neighbour records cross it
+    ((12, 10, 3), 3, [2, 2, 1], (2, 2, 3), 1, {}, (1, 1, 9)),
 ]
 IDS = ["x".join(map(str, c[0])) + "-c%d-to-" % c[1] + "x".join(map(str, c[3])) + "-b" + "x".join(map(str, np.atleast_1d(c[4])))
        + ("-ic" if c[5].get("train_inverse_cov") else "") + ("-mode2" if c[5].get("quantization_mode") else "") for c in CASES]
 
 
-def _grid_of(shape):
-    return (3, 4) if len(shape) == 2 else (2, 3, 2)
+def _grid_of(case):
+    """the block grid of a case: its own (seventh entry), or the suite's for its dimension"""
+    return case[6] if len(case) > 6 else ((3, 4) if len(case[0]) == 2 else (2, 3, 2))
 
 
 @functools.lru_cache(maxsize=None)
 def _inputs(i):
     """parameters drawn as tests/test_gpu_render.py draws them, for a FULL block grid; the restatement in both precisions"""
-    shape, C_, kpd, m, beta, kw = CASES[i]
-    grid = _grid_of(shape)
+    shape, C_, kpd, m, beta, kw = CASES[i][:6]
+    grid = _grid_of(CASES[i])
     B = int(np.prod(grid))
     cfg, p, _, K = _setup(shape, C_, kpd, C_ == 3, B, 100 + len(shape) + C_, **kw)
     active = np.random.default_rng(5).uniform(size=(B, K)) < 0.85
@@ -62,16 +68,12 @@ def _inputs(i):
     return cfg, p, K, active, grid, tabs, ref, ref64
 
 
-def _bits(active):
-    return torch.from_numpy(_mask_to_bits(active).view(np.int32)).cuda()
-
-
 # ---------------------------------------------------------------------------------------------------------------
 # 1. parity with the restatement
 # ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("i", range(len(CASES)), ids=IDS)
 def test_parity_with_the_restatement(i):
-    shape, C_, kpd, m, beta, kw = CASES[i]
+    shape, C_, kpd, m, beta, kw = CASES[i][:6]
     cfg, p, K, active, grid, tabs, ref, ref64 = _inputs(i)
     B = int(np.prod(grid))
     lsb = 1.0 / 255
@@ -106,7 +108,7 @@ def test_parity_with_the_restatement(i):
 # ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("i", range(len(CASES)), ids=IDS)
 def test_identity_with_render(i):
-    shape, C_, kpd, m, beta, kw = CASES[i]
+    shape, C_, kpd, m, beta, kw = CASES[i][:6]
     cfg, p, K, active, grid, tabs, ref, _ = _inputs(i)
     eng = _engine(shape, C_, K, use_yuv=(C_ == 3), **kw)
     dp, act, axes = _to_dev(p), _bits(active), _dev_axes(tabs)
@@ -178,7 +180,7 @@ SENT = -7.0
 @pytest.mark.parametrize("i", [1, 4, 6], ids=[IDS[i] for i in [1, 4, 6]])
 def test_shards_and_bounds(i):
     from steered_mixture_of_experts_amd import _lib
-    shape, C_, kpd, m, beta, kw = CASES[i]
+    shape, C_, kpd, m, beta, kw = CASES[i][:6]
     cfg, p, K, active, grid, tabs, ref, _ = _inputs(i)
     B = int(np.prod(grid))
     eng = _engine(shape, C_, K, use_yuv=(C_ == 3), **kw)
@@ -251,7 +253,6 @@ def test_facade_blend_on_the_device():
     """Smoe.render(blend=) on the device equals the engine's render_blend, leaves blend = 0 as it was, and changes only
     samples within the band."""
     from steered_mixture_of_experts_amd.smoe import Adam, Smoe
-    from test_gpu_render import _image
     img = _image(40, 52, C_=3, seed=3)
     s = Smoe(img, train_inverse_cov=False, kernels_per_dim=[2, 2], batch_size=[16, 16], use_determinant=True, use_yuv=True)
     s.set_optimizer(Adam(1e-3), Adam(1e-5), Adam(1.0))

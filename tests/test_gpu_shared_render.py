@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from oracle import smoe_oracle as o
+from render_cases import _bits, _dev_axes, _guarded, _owned
 from render_engine import place_blocks
 from shared_render_engine import OracleSharedRenderEngine, ids_of, oracle_shared_batches
 from steered_mixture_of_experts_amd import blocks as blk
@@ -99,30 +100,12 @@ def _dev(p):
     return {k: torch.from_numpy(np.ascontiguousarray(v[0])).cuda() for k, v in p.items()}
 
 
-def _bits(mask):
-    NB, K = mask.shape
-    out = np.zeros((NB, (K + 31) // 32), np.uint32)
-    for k in range(K):
-        out[:, k >> 5] |= (mask[:, k].astype(np.uint32) << np.uint32(k & 31))
-    return out
-
-
 def _dev_lists(mask):
-    return torch.from_numpy(_bits(mask).view(np.int32)).cuda()
+    return _bits(mask, words=True)
 
 
 def _tables(shape, extent):
     return [blk.render_axis(n, e) for n, e in zip(shape, extent)]
-
-
-def _dev_axes(tabs):
-    return [torch.from_numpy(np.ascontiguousarray(t)).cuda() for t in tabs]
-
-
-def _owned(m, grid, first, count):
-    extent = [g * v for g, v in zip(grid, m)]
-    own = np.zeros(tuple(extent) + (1,), dtype=bool)
-    return place_blocks(np.ones((count, int(np.prod(m)), 1), dtype=bool), m, grid, extent, first, own)[..., 0]
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -150,7 +133,7 @@ def test_identity_with_shared_forward(case):
     assert np.array_equal(out.view(np.uint32), want.view(np.uint32))                     # bit for bit
     have = ids >= 0
     assert np.array_equal(ids[have], want_ids[have])
-    dead = _owned(bshape, _grid(shape, bshape), EMPTY, 1)
+    dead = _owned(bshape, _grid(shape, bshape), shape, EMPTY, 1)
     assert (ids[dead] == -1).all() and (out[dead] == 0).all()                            # the empty list: 0, marker -1
     assert have[~dead].mean() > 0.99
     eng.close()
@@ -200,7 +183,7 @@ def _assert_parity(got, R, m, first, count, C_):
     """criterion 8 on the positions of the batches [first, first + count)"""
     grid = R["grid"]
     extent = [g * v for g, v in zip(grid, m)]
-    own = _owned(m, grid, first, count)
+    own = _owned(m, grid, extent, first, count)
     want = place_blocks(R["ref"]["recon"].astype(np.float32), m, grid, extent, first, np.zeros(tuple(extent) + (C_,), np.float32))
     loose_img = place_blocks(R["loose"], m, grid, extent, first, np.zeros(tuple(extent) + (C_,), bool))
     dd = np.abs(got - want)[own]
@@ -241,12 +224,6 @@ def test_parity_on_resampled_grids(case):
 # 9. shards, bounds, workgroup split
 # ---------------------------------------------------------------------------------------------------------------
 SENT = -7.0
-
-
-def _guarded(shape, dtype, fill, guard=64, shift=0):
-    n = int(np.prod(shape))
-    buf = torch.full((guard + n + guard + 8,), fill, dtype=dtype, device="cuda")
-    return buf, buf[guard + shift: guard + shift + n].view(*shape)
 
 
 SHARDS = [(IMAGES[0], (48, 40)), (IMAGES[1], (32, 32)), (IMAGES[3], (16, 16, 7))]      # 2 tiles / 1 tile / 2 tiles per batch
@@ -302,7 +279,7 @@ def test_shards_bounds_and_split(image, m, monkeypatch):
     abuf3, aview3 = _guarded(tuple(extent), torch.int32, 77)
     assert call(a_, b_ - a_, view3, aview3) == 0
     torch.cuda.synchronize()
-    own = _owned(m, grid, a_, b_ - a_)
+    own = _owned(m, grid, extent, a_, b_ - a_)
     part, part_ids = view3.cpu().numpy(), aview3.cpu().numpy()
     assert np.array_equal(part[own].view(np.uint32), whole[own].view(np.uint32)) and (part[~own] == SENT).all()
     assert np.array_equal(part_ids[own], whole_ids[own]) and (part_ids[~own] == 77).all()
