@@ -246,6 +246,38 @@ int smoe_render_blend(smoe_handle h, int32_t first_block, int32_t num_blocks, co
                       const int64_t extent[3], const float blend[3], void* image, int32_t image_format, uint8_t* argmax,
                       void* stream);
 
+/* Viewport decode: an axis-aligned window of the image on a "ragged separable grid" that owes nothing to the block grid,
+ * into a dense image [E_0, E_1(, E_2), C] that holds the window and nothing else.  Per axis l:
+ *   view_first[l], view_blocks[l]   the blocks view_first .. view_first + view_blocks - 1 of the axis form the box of the view
+ *   axis_start[l]            HOST array of view_blocks[l] + 1 int32: start[0] = 0, non-decreasing, start[view_blocks[l]] = E_l
+ *                            >= 1.  Output indices [start[j], start[j + 1]) lie in block view_first[l] + j; empty runs are legal
+ *                            (a thumbnail skips blocks) and cost nothing.  Read during the call only
+ *   axis_coords[l]           DEVICE table of E_l fp32 coordinates, each in the block units of the block that owns the sample
+ *                            (the unit of smoe_render's tables).  The kernel computes no coordinates
+ * Sample (i_0, i_1(, i_2)) is evaluated by the block whose per-axis indices own i_l (image-wide index row-major over grid[])
+ * at (coords_0[i_0], ...) exactly as smoe_render evaluates a sample of that block; every position of the image is written.
+ *   p, active                cover ALL prod(grid) blocks, indexed by the image-wide block index, as does the centre grid of
+ *                            smoe_set_center_grid; only the blocks of the box with a non-empty run on every axis and, with
+ *                            blend, their neighbours inside the image are read
+ *   blend                    NULL, or per-axis half-widths in source pixels with the checks and the meaning of
+ *                            smoe_render_blend (same windows, neighbour coordinates, drop of blocks without influence, single
+ *                            rounding).  NULL, all zero, or block_shape[l] == 1 on every blended axis: no blending
+ *   image_format, argmax     as smoe_render (argmax: uint8 local kernel id of the own block, 255 = none)
+ * The hoisting level is the one smoe_render takes for prod(grid) blocks (the tiling of the whole image), so a view on
+ * blocks.render_axis coordinates is bit-identical to the same positions of smoe_render / smoe_render_blend.  Results do not
+ * depend on how the launch cuts the view into workgroups.  Offsets into the image are 64-bit; stores are 16 bytes wide where
+ * image / argmax are 16-byte aligned, element-wise at ragged heads and tails.
+ * Limits: E_l <= 2^31 - 1; a block's run may have any length.  A workgroup takes a tile of the view (at most 256 innermost
+ * samples, at most 1024 outer tuples) and stages only the tile's part of the tables and the derived records of the blocks the
+ * tile touches.  SMOE_ERR_UNSUPPORTED: the derived records of the smallest tile (one block, with blend 3 per blended axis)
+ * pass 48 KB, the tile does not fit 160 KB of LDS, the launch would need 2^31 or more workgroups, or SMOE_IMAGE_U8 with
+ * precision > 8.  The call uploads its tiling table into a workspace of the handle on `stream`: calls of one handle must be
+ * ordered on one stream (as every entry point that uses the handle's workspaces). */
+int smoe_render_view(smoe_handle h, const smoe_params* p, const uint32_t* active, const int32_t grid[3],
+                     const int32_t view_first[3], const int32_t view_blocks[3], const int32_t* const axis_start[3],
+                     const float* const axis_coords[3], const float blend[3], void* image, int32_t image_format,
+                     uint8_t* argmax, void* stream);
+
 /* Name of the kernel variant smoe_fit would launch for num_blocks (diagnostics / profiles). */
 const char* smoe_fit_variant(smoe_handle h, int32_t num_blocks);
 

@@ -7,6 +7,8 @@ t innermost.  Every block is its own [0,1]^d domain (smoe.py:2412), i.e. ``block
 """
 from __future__ import annotations
 
+import math
+from fractions import Fraction
 from typing import Dict, List, Sequence, Tuple
 
 import numpy as np
@@ -84,6 +86,67 @@ def render_axis(n: int, m: int) -> np.ndarray:
         return np.linspace(0, 1, n).astype(np.float32)
     j = np.arange(m, dtype=np.float64)
     return (((j + 0.5) * n / m - 0.5) / (n - 1)).astype(np.float32)
+
+
+def _round_once_f32(x: Fraction) -> np.float32:
+    """The float32 nearest to the exact ``x`` (ties to even): float64 first, then repaired where that second rounding
+    starts from a float64 that sits exactly half way between two float32 while ``x`` itself does not."""
+    d = float(x)
+    r = np.float32(d)
+    if float(r) != d:
+        other = np.nextafter(r, np.float32(np.inf) if d > float(r) else np.float32(-np.inf))
+        mid = (Fraction(float(r)) + Fraction(float(other))) / 2
+        if Fraction(d) == mid and x != mid:
+            r = other if (x > mid) == (float(other) > float(r)) else r
+    return r
+
+
+def view_axis(n: int, grid_l: int, length_l, lo, hi, E: int):
+    """One axis of a viewport (``Smoe.render_view``, include/smoe_hip.h: smoe_render_view): ``E`` samples over the window
+    ``[lo, hi)`` of an axis of ``length_l`` source pixels cut into ``grid_l`` blocks of ``n`` pixels.  Pixel-footprint
+    convention of ``render_axis``: source pixel ``q`` covers ``[q, q + 1)``, ``0 <= lo < hi <= length_l``.  Sample ``i``
+    sits at ``x_i = lo + (i + 0.5)(hi - lo) / E``, in block ``g = min(floor(x_i / n), grid_l - 1)``, at the block-unit
+    coordinate ``(x_i - g n - 0.5) / (n - 1)`` (0 for ``n == 1``), computed exactly and rounded to float32 once.  Where a
+    block's run coincides with ``render_axis(n, m)`` for an integer ``m`` (the pitch is ``n / m`` and the run's first
+    sample is one of that table's) the values are THAT table's, so an aligned view is bit-identical to ``render``.
+    Returns ``(first, blocks, start, coords)``: the first block of the view, the number of blocks it spans,
+    ``start`` int32 ``[blocks + 1]`` (samples ``[start[j], start[j + 1])`` lie in block ``first + j``; runs may be empty)
+    and ``coords`` float32 ``[E]``."""
+    n, grid_l, E = int(n), int(grid_l), int(E)
+    if n < 1 or grid_l < 1:
+        raise ValueError("view_axis: n and grid_l must be >= 1")
+    if E < 1 or E > 2 ** 31 - 1:
+        raise ValueError("view_axis: E must be 1 .. 2^31 - 1")
+    lo, hi, length = float(lo), float(hi), float(length_l)
+    if not (0.0 <= lo < hi <= length) or length > grid_l * n:
+        raise ValueError(f"view_axis: the window must satisfy 0 <= lo < hi <= length ({lo}, {hi}, {length})")
+    flo, pitch = Fraction(lo), (Fraction(hi) - Fraction(lo)) / E
+    # x_i = (P + (2 i + 1) Q) / R in integers: no fraction is reduced per sample
+    half = pitch / 2
+    R = math.lcm(flo.denominator, half.denominator)
+    P, Q = flo.numerator * (R // flo.denominator), half.numerator * (R // half.denominator)
+    nums = [P + (2 * i + 1) * Q for i in range(E)]
+    gs = np.fromiter((min(v // (R * n), grid_l - 1) for v in nums), dtype=np.int64, count=E)
+    first, blocks = int(gs[0]), int(gs[-1] - gs[0] + 1)
+    start = np.searchsorted(gs, first + np.arange(blocks + 1), side="left").astype(np.int32)
+    coords = np.zeros((E,), dtype=np.float32)
+    if n == 1:
+        return first, blocks, start, coords
+    m = Fraction(n) / pitch
+    table = render_axis(n, int(m)) if m.denominator == 1 else None
+    for j in range(blocks):
+        a, b = int(start[j]), int(start[j + 1])
+        if a == b:
+            continue
+        g = first + j
+        if table is not None:
+            j0 = (Fraction(nums[a], R) - g * n) / pitch - Fraction(1, 2)
+            if j0.denominator == 1 and 0 <= j0 and int(j0) + (b - a) <= len(table):
+                coords[a:b] = table[int(j0):int(j0) + (b - a)]
+                continue
+        for i in range(a, b):
+            coords[i] = _round_once_f32((Fraction(nums[i], R) - g * n - Fraction(1, 2)) / (n - 1))
+    return first, blocks, start, coords
 
 
 def to_planar(blocks: np.ndarray) -> np.ndarray:

@@ -2654,7 +2654,8 @@ int fit_occupancy(int N, bool has_lw, int hoist, bool pair) {
       team_fit_ptr<D, C, K, G, W>(), team_lds_ptr<D, C, K, G, W>(), team_occ_ptr<D, C, K, G, W>(), \
       duo_fit_ptr<D, C, K, G>(), duo_lds_ptr<D, C, K, G>(), duo_occ_ptr<D, C, K, G>(), \
       &launch_render<D, C, K, (SMOE_FULL != 0)>, &launch_render_blend<D, C, K, (SMOE_FULL != 0)>, \
-      &render_layout<D, C, K, (SMOE_FULL != 0)>, &render_blend_layout<D, C, K, (SMOE_FULL != 0)> }
+      &render_layout<D, C, K, (SMOE_FULL != 0)>, &render_blend_layout<D, C, K, (SMOE_FULL != 0)>, \
+      &render_view_layout<D, C, K, (SMOE_FULL != 0)>, &launch_render_view<D, C, K, (SMOE_FULL != 0)> }
 
 }  // namespace smoe
 #endif

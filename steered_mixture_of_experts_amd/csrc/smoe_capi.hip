@@ -22,6 +22,9 @@ struct smoe_context {
     float* d_probes;     // [D][3]
     float* d_ssim_T;     // ssim_opt: banded tap tables Tr [bh][11], Tc [bw][11]
     double* d_partials;  // workspace of smoe_reduce_scalars
+    int32_t* d_view;     // workspace of smoe_render_view: the tiling table of the last call (view_cap entries)
+    size_t view_cap;
+    std::vector<int32_t> view_tab;   // the host copy of that table: alive for as long as its upload may read it
     uint32_t* d_dbg;     // SMOE_DEBUG build: word the kernels' device-side checks report into (null otherwise)
     int force_g;
     const float* mus_grid;   // use_diff_center: kernel-grid centres [B,K,D] of the blocks the calls pass (smoe_set_center_grid), or null
@@ -628,6 +631,7 @@ int smoe_destroy(smoe_handle h) {
     if (h->d_probes) dev_free(h->d_probes);
     if (h->d_ssim_T) dev_free(h->d_ssim_T);
     if (h->d_partials) dev_free(h->d_partials);
+    if (h->d_view) dev_free(h->d_view);
     if (h->d_dbg) dev_free(h->d_dbg);
     delete h;
     return SMOE_OK;
@@ -936,6 +940,102 @@ int smoe_render_blend(smoe_handle h, int32_t first_block, int32_t num_blocks, co
     (void)stream;
     smoe::RenderLayout lay;
     return decoder_launched(fn, v->render_blend_layout(b, hl, v->G, lay), kRenderUnsupported);
+#endif
+}
+
+int smoe_render_view(smoe_handle h, const smoe_params* p, const uint32_t* active, const int32_t grid[3],
+                     const int32_t view_first[3], const int32_t view_blocks[3], const int32_t* const axis_start[3],
+                     const float* const axis_coords[3], const float blend[3], void* image, int32_t image_format,
+                     uint8_t* argmax, void* stream) {
+    const std::string fn = "smoe_render_view";
+    if (!h) return fail(SMOE_ERR_INVALID, fn + ": null handle");
+    if (!params_ok(p)) return fail(SMOE_ERR_INVALID, fn + ": p (all six parameter tensors) is required");
+    if (!image) return fail(SMOE_ERR_INVALID, fn + ": image is required");
+    if (!grid) return fail(SMOE_ERR_INVALID, fn + ": grid is required");
+    if (!view_first) return fail(SMOE_ERR_INVALID, fn + ": view_first is required");
+    if (!view_blocks) return fail(SMOE_ERR_INVALID, fn + ": view_blocks is required");
+    if (!axis_start) return fail(SMOE_ERR_INVALID, fn + ": axis_start is required");
+    if (!axis_coords) return fail(SMOE_ERR_INVALID, fn + ": axis_coords is required");
+    if (image_format != SMOE_IMAGE_F32 && image_format != SMOE_IMAGE_U8)
+        return fail(SMOE_ERR_INVALID, fn + ": image_format must be SMOE_IMAGE_F32 or SMOE_IMAGE_U8");
+    const int D = h->cfg.dim;
+    long long total = 1;
+    int64_t ext[3] = {1, 1, 1};
+    for (int l = 0; l < D; ++l) {
+        const std::string ax = "[" + std::to_string(l) + "]";
+        if (!axis_start[l]) return fail(SMOE_ERR_INVALID, fn + ": axis_start" + ax + " is null");
+        if (!axis_coords[l]) return fail(SMOE_ERR_INVALID, fn + ": axis_coords" + ax + " is null");
+        if (grid[l] < 1) return fail(SMOE_ERR_INVALID, fn + ": grid" + ax + " must be >= 1");
+        total *= grid[l];
+        if (total > 0x7fffffffLL) return fail(SMOE_ERR_INVALID, fn + ": grid has more than 2^31 blocks");
+        if (view_first[l] < 0) return fail(SMOE_ERR_INVALID, fn + ": view_first" + ax + " must be >= 0");
+        if (view_blocks[l] < 1) return fail(SMOE_ERR_INVALID, fn + ": view_blocks" + ax + " must be >= 1");
+        if ((long long)view_first[l] + view_blocks[l] > grid[l])
+            return fail(SMOE_ERR_INVALID, fn + ": view_first" + ax + " + view_blocks" + ax + " exceeds grid" + ax);
+        const int32_t* st = axis_start[l];
+        if (st[0] != 0) return fail(SMOE_ERR_INVALID, fn + ": axis_start" + ax + "[0] must be 0");
+        for (int j = 0; j < view_blocks[l]; ++j)
+            if (st[j + 1] < st[j]) return fail(SMOE_ERR_INVALID, fn + ": axis_start" + ax + " must not decrease");
+        if (st[view_blocks[l]] < 1) return fail(SMOE_ERR_INVALID, fn + ": axis_start" + ax + " must end at E >= 1");
+        ext[l] = st[view_blocks[l]];
+    }
+    bool any = false;
+    if (blend) {
+        for (int l = 0; l < D; ++l) {
+            const int n = h->cfg.block_shape[l];
+            if (!std::isfinite(blend[l]) || blend[l] < 0.0f || blend[l] > 0.5f * (float)n)
+                return fail(SMOE_ERR_INVALID, fn + ": blend[" + std::to_string(l) + "] must be finite and within 0 .. block_shape / 2");
+            any = any || (blend[l] > 0.0f && n > 1);
+        }
+    }
+    if (image_format == SMOE_IMAGE_U8 && h->cfg.precision > 8)
+        return fail(SMOE_ERR_UNSUPPORTED, fn + ": SMOE_IMAGE_U8 needs precision <= 8");
+
+    // a sample must come out as smoe_render's for the whole image: the tiling and hoisting level of prod(grid) blocks
+    const smoe::Variant* v = nullptr;
+    int hl = 0;
+    const int rp = render_plan(h, fn.c_str(), (int32_t)total, &v, &hl);
+    if (rp != SMOE_OK) return rp;
+    if (!v->render_view || !v->render_view_layout) return fail(SMOE_ERR_UNSUPPORTED, fn + ": no kernel variant for this handle");
+    smoe::RenderViewArgs a;
+    std::memset(&a, 0, sizeof a);
+    const int32_t whole[3] = {1, 1, 1};
+    a.r = render_args(h, 0, (int32_t)total, *p, active, h->mus_grid, axis_coords, whole, grid, ext, image, image_format, argmax);
+    smoe::ViewHost hst;
+    std::memset(&hst, 0, sizeof hst);
+    for (int l = 0; l < D; ++l) {
+        hst.start[l] = axis_start[l]; hst.first[l] = view_first[l]; hst.blocks[l] = view_blocks[l];
+        const int n = h->cfg.block_shape[l];
+        if (!any || n < 2 || !(blend[l] > 0.0f)) continue;
+        a.s0[l] = (float)(-0.5 / (n - 1));
+        a.s1[l] = (float)(1.0 + 0.5 / (n - 1));
+        a.band[l] = (float)((double)blend[l] / (n - 1));
+        a.pitch[l] = (float)((double)n / (n - 1));
+    }
+    smoe::ViewPlan plan;
+    smoe::RenderLayout lay;
+    const int rc = decoder_launched(fn, v->render_view_layout(a, hst, plan, hl, lay), kRenderUnsupported);
+    if (rc != SMOE_OK) return rc;
+    // the table of the launch into the handle's workspace, ordered on the stream in front of the kernel
+    if (plan.tab.size() > h->view_cap) {
+        if (h->d_view) dev_free(h->d_view);
+        h->d_view = nullptr;
+        h->view_cap = 0;
+        const size_t cap = plan.tab.size() + plan.tab.size() / 2 + 256;
+        const hipError_t e = dev_malloc(&h->d_view, sizeof(int32_t) * cap);
+        if (e != hipSuccess) return fail_hip(e, "smoe_render_view: workspace");
+        h->view_cap = cap;
+    }
+    a.tab = h->d_view;
+    h->view_tab.swap(plan.tab);
+#if !SMOE_HOST_TEST
+    HIP_TRY(hipMemcpyAsync(h->d_view, h->view_tab.data(), sizeof(int32_t) * h->view_tab.size(), hipMemcpyHostToDevice, (hipStream_t)stream),
+            "smoe_render_view: table upload");
+    return decoder_launched(fn, v->render_view(a, lay, (hipStream_t)stream), kRenderUnsupported);
+#else
+    (void)stream;
+    (void)dev_upload(h->d_view, h->view_tab.data(), sizeof(int32_t) * h->view_tab.size());
+    return SMOE_OK;
 #endif
 }
 

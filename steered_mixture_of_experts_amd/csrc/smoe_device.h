@@ -7,6 +7,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "smoe_hip.h"
 
 namespace smoe {
@@ -158,6 +160,35 @@ struct RenderBlendArgs {
     int off_w;                                  // float offset of the neighbour-weight tables in the dynamic LDS (launcher)
 };
 
+// smoe_render_view (smoe_render_view.hip.h): a window of the image on a ragged separable sample grid.  r.p / r.active /
+// r.mus_grid cover ALL prod(grid) blocks (image-wide block index); r.ax[l]: the E_l coordinates of axis l; r.ext[l] = E_l;
+// r.CL / r.RP: columns of a tile / rows per step; r.off_par / r.off_stage: the derived records / the staging buffers.
+struct RenderViewArgs {
+    RenderArgs r;
+    float s0[SMOE_MAX_DIM], s1[SMOE_MAX_DIM], band[SMOE_MAX_DIM], pitch[SMOE_MAX_DIM];   // as in RenderBlendArgs; band 0: no blend on the axis
+    const int32_t* tab;       // device table of the launch (ViewPlan::tab); per axis, at these offsets:
+    int o_ent_start[SMOE_MAX_DIM];   // [entries + 1] first sample of every non-empty run ("entry"), then E_l
+    int o_ent_slot[SMOE_MAX_DIM];    // [entries] the entry's block in the axis' record list
+    int o_rec_block[SMOE_MAX_DIM];   // [slots] block index on the axis of every record slot: the entries' blocks, ascending, with a
+                                     // blend on the axis also their neighbours inside the image
+    int o_tile_s[SMOE_MAX_DIM];      // [tiles + 1] first sample of every tile, then E_l
+    int o_tile_e[SMOE_MAX_DIM];      // [tiles][2] the entries [first, end) a tile touches
+    int ntiles[SMOE_MAX_DIM];
+    int TS[SMOE_MAX_DIM];            // samples of the largest tile on the axis: the size of its LDS tables
+    int off_ax[SMOE_MAX_DIM];        // float offset of the axis' tables in the dynamic LDS
+};
+
+// the host tables of a view as the caller of smoe_render_view passed them
+struct ViewHost {
+    const int32_t* start[SMOE_MAX_DIM];
+    int32_t first[SMOE_MAX_DIM], blocks[SMOE_MAX_DIM];
+};
+
+// what render_view_layout makes for the device next to the geometry fields of RenderViewArgs
+struct ViewPlan {
+    std::vector<int32_t> tab;
+};
+
 // What the launcher of a block decoder derives from checked arguments, next to the geometry fields of RenderArgs (and off_w
 // of RenderBlendArgs) it fills: a pure host computation (render_layout / render_blend_layout), also run without a device
 struct RenderLayout {
@@ -200,6 +231,10 @@ struct Variant {
     // the launch geometry of the two decoders alone: what render / render_blend compute before they launch, for the same arguments
     hipError_t (*render_layout)(RenderArgs&, int hl, int lanes, RenderLayout&);
     hipError_t (*render_blend_layout)(RenderBlendArgs&, int hl, int lanes, RenderLayout&);
+    // viewport decoder (smoe_render_view.hip.h): the plan of a view (tiling, device table, LDS carve-up: pure host code), and the
+    // launch of a planned view whose table is on the device
+    hipError_t (*render_view_layout)(RenderViewArgs&, const ViewHost&, ViewPlan&, int hl, RenderLayout&);
+    hipError_t (*render_view)(const RenderViewArgs&, const RenderLayout&, hipStream_t);
 };
 
 // ---- shared-kernel image mode (smoe_shared.hip) ----------------------------------------------

@@ -372,6 +372,55 @@ class BlockEngine(_Engine):
         return self._render("render_blend", entry, params, active, total, axes, grid, extent, first_block, B, out, dtype,
                             want_argmax, blend)
 
+    def render_view(self, params, active, grid, view_first, starts, axes, blend=None, out=None, dtype=torch.float32,
+                    want_argmax=False, center_grid=None):
+        """Viewport decode (include/smoe_hip.h: smoe_render_view): the window of the image that the per-axis tables describe,
+        into a dense image ``[E_0, E_1(, E_2), C]``.  ``starts[l]``: HOST int32 table of ``view_blocks[l] + 1`` entries
+        (samples ``[start[j], start[j + 1])`` lie in block ``view_first[l] + j``; ``start[-1] = E_l``); ``axes[l]``: float32
+        device table of the ``E_l`` coordinates in block units (``blocks.view_axis`` makes both).  ``params``, ``active`` and
+        ``center_grid`` cover ALL ``prod(grid)`` blocks, as in ``render_blend``; ``blend``: None or render_blend's.  Returns
+        the image, with ``want_argmax`` also the uint8 map of the own block's kernel ids (255: none)."""
+        d = self.cfg.dim
+        who = "render_view"
+        grid = [int(g) for g in grid]
+        view_first = [int(g) for g in view_first]
+        self._check_render_arity(who, dtype, axes, (grid, view_first, starts), "axes, grid, view_first and starts")
+        total = 1
+        for g in grid:
+            total *= g
+        self._check_params(params, total)
+        if active is not None and (tuple(active.shape) != (total,) or active.dtype != torch.int32 or active.device != self.device):
+            raise ValueError(f"{who}: active must be int32 [{total}] on {self.device}")
+        st = [np.ascontiguousarray(np.asarray(t), dtype=np.int32) for t in starts]
+        if any(t.ndim != 1 or t.size < 2 for t in st):
+            raise ValueError(f"{who}: every start table needs view_blocks + 1 >= 2 entries")
+        extent = [int(t[-1]) for t in st]
+        if min(extent) < 1:
+            raise ValueError(f"{who}: every axis needs at least one sample")
+        self._check_axis_tables(who, axes, extent)
+        bl = None
+        if blend is not None:
+            bl = [float(v) for v in np.atleast_1d(blend)]
+            bl = bl * d if len(bl) == 1 else bl
+            if len(bl) != d:
+                raise ValueError(f"{who}: blend needs one value or {d}")
+        out, fmt, am = self._render_planes(out, extent, dtype, True, want_argmax, 255, torch.uint8)
+        cp = self._cparams(params)
+        held = getattr(self, "_center_grid", None)
+        if center_grid is not None:                          # the image-wide centre grid around the launch alone
+            self.set_center_grid(center_grid)
+        try:
+            rc = self.lib.smoe_render_view(
+                self._h, C.byref(cp), _ptr(active), _slots(C.c_int32, grid, 1), _slots(C.c_int32, view_first, 0),
+                _slots(C.c_int32, [t.size - 1 for t in st], 1), _slots(C.c_void_p, [t.ctypes.data for t in st], None),
+                self._axis_slots(axes), None if bl is None else _slots(C.c_float, bl, 0.0), _ptr(out), fmt, _ptr(am),
+                self._stream())
+        finally:
+            if center_grid is not None:
+                self.set_center_grid(held)
+        _lib.check(rc)
+        return (out, am) if want_argmax else out
+
     def fit(self, target, params, state: AdamState, active, n_iters: int, loss_w=None, diverged=None,
             loss0=None, loss_out=None, sse_out=None, loss_w_is_sample=False):
         """loss_w_is_sample: ``loss_w`` is a pixel sub-sample (N / n for the drawn pixels, 0 otherwise; smoe.py:1664-1667):

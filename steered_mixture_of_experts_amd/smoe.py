@@ -807,6 +807,82 @@ class Smoe(_SmoeBase):
         return self._render(scale, samples_per_block, dtype, quantized, want_argmax, to_host,
                             blend=bl if any(v > 0 for v in bl) else None)
 
+    def render_view(self, window, size=None, scale=None, dtype=np.float32, quantized=False, want_argmax=False,
+                    to_host=True, blend=0.0):
+        """Decode a viewport: the axis-aligned ``window`` of the image domain at the output ``size``, on the device (the
+        engine's ``render_view``; include/smoe_hip.h: smoe_render_view).  Only the window is computed and stored: an 8x
+        detail, a fit-to-window zoom of any ratio, a thumbnail with fewer samples than blocks, one frame of a video.
+        ``window``: one ``(lo, hi)`` per axis in source pixels (pixel ``q`` covers ``[q, q + 1)``, ``0 <= lo < hi <=
+        image.shape[l]``; None for an axis: the whole axis).  ``size``: the ``E_l`` output samples per axis, or ``scale``
+        (a number or one per axis): ``E_l = max(1, round((hi - lo) * scale_l))``; not both, neither: scale 1.  Sample
+        positions: ``blocks.view_axis`` -- a window that is a crop of a ``render`` grid gives exactly that crop.
+        ``dtype``, ``quantized``, ``blend`` and the global ids of ``want_argmax`` (int64, -1: none) are ``render``'s; the
+        kernel lists are ``render``'s too.  Returns the image ``[*E, C]``.  Several ranks: parameters and lists are gathered
+        and every rank renders the whole view (a view is small); the result is the same on every rank and for every
+        number of ranks."""
+        d, n = self.dim_domain, self.batch_size_valued
+        bl = [float(v) for v in np.atleast_1d(blend)]
+        bl = bl * d if len(bl) == 1 else bl
+        if len(bl) != d:
+            raise ValueError(f"render_view: blend needs one value or {d}")
+        for v, nl in zip(bl, n):
+            if not np.isfinite(v) or v < 0 or v > nl / 2:
+                raise ValueError("render_view: blend must lie within 0 .. block size / 2 on every axis")
+        window = [None] * d if window is None else list(window)
+        if len(window) != d:
+            raise ValueError(f"render_view: window needs one (lo, hi) per axis ({d})")
+        win = [(0.0, float(self.image.shape[l])) if w is None else (float(w[0]), float(w[1])) for l, w in enumerate(window)]
+        for l, (lo, hi) in enumerate(win):
+            if not (0.0 <= lo < hi <= float(self.image.shape[l])):
+                raise ValueError(f"render_view: window[{l}] must satisfy 0 <= lo < hi <= {int(self.image.shape[l])}")
+        if size is not None and scale is not None:
+            raise ValueError("render_view: give size or scale, not both")
+        if size is not None:
+            E = [int(v) for v in np.atleast_1d(size)]
+            E = E * d if len(E) == 1 else E
+            if len(E) != d or min(E) < 1:
+                raise ValueError(f"render_view: size needs {d} entries >= 1")
+        else:
+            sc = list(np.atleast_1d(1 if scale is None else scale))
+            sc = sc * d if len(sc) == 1 else sc
+            if len(sc) != d:
+                raise ValueError(f"render_view: scale needs one value or {d}")
+            E = [max(1, int(round((hi - lo) * float(v)))) for (lo, hi), v in zip(win, sc)]
+        npdt = np.dtype(dtype)
+        if npdt not in (np.dtype(np.float32), np.dtype(np.uint8)):
+            raise ValueError("render_view: dtype must be float32 or uint8")
+        tdt = torch.uint8 if npdt == np.dtype(np.uint8) else torch.float32
+        eng = self._engine
+        if not hasattr(eng, "render_view"):
+            raise NotImplementedError("this engine has no render_view()")
+        dev = eng.device
+        tabs = [blk.view_axis(n[l], self.grid[l], self.image.shape[l], win[l][0], win[l][1], E[l]) for l in range(d)]
+        params = self._quantized_params() if quantized else self._params
+        active = self._render_lists(quantized)
+        center = None
+        if self.world_size > 1:
+            full = lambda t: torch.from_numpy(np.ascontiguousarray(sdist.allgather_blocks(t.cpu().numpy(), self.num_blocks))).to(dev)
+            params = {k: full(v) for k, v in params.items()}
+            active = None if active is None else full(active)
+            if self._mus_grid is not None and int(self.quantization_mode) >= 2:
+                center = torch.from_numpy(np.ascontiguousarray(sdist.allgather_blocks(self._mus_grid, self.num_blocks),
+                                                               dtype=np.float32)).to(dev)
+        res = eng.render_view(params, active, self.grid, [t[0] for t in tabs], [t[2] for t in tabs],
+                              [torch.from_numpy(t[3]).to(dev) for t in tabs], blend=bl if any(v > 0 for v in bl) else None,
+                              dtype=tdt, want_argmax=want_argmax, center_grid=center)
+        img, ids = res if want_argmax else (res, None)
+        if ids is not None:
+            # the block of every position from the start tables
+            pos = [torch.from_numpy(t[0] + np.repeat(np.arange(t[1]), np.diff(t[2]))).to(dev) for t in tabs]
+            bid = pos[0]
+            for l in range(1, d):
+                bid = bid.reshape(bid.shape + (1,)) * self.grid[l] + pos[l]
+            ids = self._global_ids(ids.to(torch.int64), bid, torch.ones_like(bid, dtype=torch.bool))
+        if to_host:
+            img = img.cpu().numpy()
+            ids = None if ids is None else ids.cpu().numpy()
+        return (img, ids) if want_argmax else img
+
     # hooks of _render
     def _engine_render_blend(self, params, active, axes, grid, extent, out, tdt, want_argmax, blend):
         # the engine reads the neighbours of this rank's blocks: with several ranks, everyone's parameters and list words

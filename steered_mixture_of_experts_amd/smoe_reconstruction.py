@@ -8,6 +8,9 @@ model on another sampling grid with ``Smoe.render`` / ``SharedSmoe.render`` (per
 the device, written straight into the stitched image); with the defaults the output is the reference's.
 ``--blend B`` (source pixels, one value or one per axis; per-block models only) cross-fades neighbouring blocks within ``B``
 pixels of every block border (``Smoe.render(blend=...)``): no block seams in the enlarged image.
+``--window LO HI ...`` (two numbers per axis, source pixels) and / or ``--size E ...`` (output samples per axis) decode a
+viewport with ``Smoe.render_view``: only that window of the image, at that size (``--size`` absent: ``--scale`` times the
+window; ``--window`` absent: the whole image); they work together with ``--scale`` and ``--blend``; per-block models only.
 """
 import argparse
 import os
@@ -40,7 +43,7 @@ _shared_engine_factory = None      # tests put the oracle-backed engine here; No
 
 
 def main(image_path, results_path, params_file, batches=1, bit_depths=(20, 18, 6, 10, 10), quant_params=False,
-         scale=None, frames=None, blend=None):
+         scale=None, frames=None, blend=None, window=None, size=None):
     if len(bit_depths) != 5:
         raise ValueError("Number of bit depths must be five!")           # smoe_reconstruction.py:17-18
     orig, precision, _ = read_image(image_path)
@@ -84,7 +87,29 @@ def main(image_path, results_path, params_file, batches=1, bit_depths=(20, 18, 6
         reconstruction = smoe.get_reconstruction()
     sc = [float(v) for v in np.atleast_1d(1.0 if scale is None else scale)]
     bl = [float(v) for v in np.atleast_1d(0.0 if blend is None else blend)]
-    if frames is not None or any(v != 1.0 for v in sc) or any(v != 0.0 for v in bl):
+    if window is not None or size is not None:
+        # a viewport: that window of the image at that size and nothing else (Smoe.render_view)
+        if not hasattr(smoe, "render_view"):
+            raise ValueError("--window / --size need a per-block model: this pickle holds a whole-image (shared-kernel) "
+                             "model, which has no viewport decoder")
+        d = smoe.dim_domain
+        if frames is not None:
+            raise ValueError("--frames does not go with --window / --size (give the time axis its own window and size)")
+        if window is not None and len(window) != 2 * d:
+            raise ValueError(f"--window takes two numbers per axis ({2 * d})")
+        if size is not None and len(size) != d:
+            raise ValueError(f"--size takes one number per axis ({d})")
+        if size is not None and scale is not None:
+            raise ValueError("--size and --scale both set the output size: give one")
+        if len(sc) not in (1, d):
+            raise ValueError(f"--scale takes one value or {d}")
+        win = None if window is None else [(float(window[2 * l]), float(window[2 * l + 1])) for l in range(d)]
+        reconstruction = smoe.render_view(win, size=None if size is None else [int(v) for v in size],
+                                          scale=None if size is not None else sc, quantized=with_q, blend=bl)
+        reconstruction_path += "_view" + "x".join(str(v) for v in reconstruction.shape[:d])
+        if any(v != 0.0 for v in bl):
+            reconstruction_path += "_blend" + "x".join("%g" % v for v in bl)
+    elif frames is not None or any(v != 1.0 for v in sc) or any(v != 0.0 for v in bl):
         # another sampling grid: evaluate the model there (Smoe.render / SharedSmoe.render); the pass above keeps loss / mse
         # as reported
         d = smoe.dim_domain
@@ -118,6 +143,10 @@ def _parser():
     parser.add_argument('--blend', type=float, default=None, nargs='+',
                         help="cross-fade neighbouring blocks within this many source pixels of a block border (one value or "
                              "one per axis, at most half a block; default 0 = off; per-block models only)")
+    parser.add_argument('--window', type=float, default=None, nargs='+',
+                        help="decode only this window of the image: LO HI per axis, in source pixels (per-block models only)")
+    parser.add_argument('--size', type=int, default=None, nargs='+',
+                        help="output samples per axis of the window (default: --scale times the window)")
     return parser
 
 
