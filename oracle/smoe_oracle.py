@@ -769,7 +769,8 @@ def shared_pass(p, target, coords, lists, cfg: OracleConfig, dtype=np.float32, w
     """One run_batched pass (smoe.py:1606-1793) in shared-kernel mode.  p: leading axis 1;
     target (NB,Nb,C); coords (NB,Nb,d); lists (NB,K) bool.  Returns the per-batch forward dict plus
     ``loss_val``/``mse_val`` (pixel-weighted means, smoe.py:1758-1759), ``lists_new`` (1763-1766)
-    and, with want_grads, ``grads`` = SUM over batches of the per-batch gradients (smoe.py:1150)."""
+    and, with want_grads, ``grads`` = SUM over batches of the per-batch gradients (smoe.py:1150); ``batch_grads`` keeps
+    the summands (leading NB)."""
     NB = target.shape[0]
     f = forward(_bcast(p, NB), target, coords, lists, cfg, loss_w, dtype, want_grads=want_grads)      # loss_w: (NB,Nb) or None
     f["loss_val"] = float(np.mean(f["loss"]))                       # equal-size batches
@@ -783,6 +784,7 @@ def shared_pass(p, target, coords, lists, cfg: OracleConfig, dtype=np.float32, w
                      cfg, None, dtype)
         f["lists_new"] = fe["active_new"]
     if want_grads:
+        f["batch_grads"] = f["grads"]
         f["grads"] = {k: np.sum(v, axis=0, keepdims=True) for k, v in f["grads"].items()}
     return f
 

@@ -175,7 +175,12 @@ class OracleEngine:
 
 
 class OracleSharedEngine:
-    """Test double of ``SharedEngine`` on the numpy oracle (shared-kernel mode), torch CPU tensors."""
+    """Test double of ``SharedEngine`` on the numpy oracle (shared-kernel mode), torch CPU tensors.
+
+    Like the library it keeps, per batch, the gradient row of the batch's last training pass (``_part``), whether that pass
+    belongs to the current step (``_seen``: cleared by ``apply`` and ``discard_gradients``) and the kernels it trained there
+    (``_trained``: listed and prior > 0).  The step itself reads the running sum in ``grad_buffer()``; the rows are there for
+    the mutants of tests/test_shared_step_parity_cpu.py, which get the sum wrong the ways a gather over rows can."""
 
     def __init__(self, cfg, device=None):
         self.cfg = cfg
@@ -199,8 +204,10 @@ class OracleSharedEngine:
         self.num_batches = self.coords.shape[0]
         self.list_words = (cfg.kernels + 31) // 32
         self.batch_pixels = self.coords.shape[1]
-        self._sizes = None
         self._buf = None
+        self._part = None
+        self._seen = np.zeros((self.num_batches,), bool)
+        self._trained = np.zeros((self.num_batches, cfg.kernels), bool)
 
     def close(self):
         pass
@@ -269,10 +276,18 @@ class OracleSharedEngine:
         tgt = np.ascontiguousarray(target.numpy().transpose(0, 2, 1))
         f = o.shared_pass(self._p(params), tgt, self.coords[first_batch:first_batch + nb], self._mask(lists), self.ocfg,
                           np.float32, want_grads=True, halo_coords=self._halo(first_batch, nb), loss_w=self._lw(first_batch, nb))
+        mask = self._mask(lists)
         self._setbits(lists, f["lists_new"])
         buf = self.grad_buffer()
         flat = np.concatenate([f["grads"][k][0].astype(np.float64).ravel() for k in NAMES])
         buf += torch.from_numpy(flat)
+        if self._part is None:
+            self._part = np.zeros((self.num_batches, flat.size), np.float32)
+        rows = slice(first_batch, first_batch + nb)
+        self._part[rows] = np.concatenate([f["batch_grads"][k].reshape(nb, -1) for k in NAMES], axis=1)
+        self._seen[rows] = True
+        graph_pis = o.quantize_graph_params(self._p(params), self.ocfg, np.float32)[0]["pis"][0]
+        self._trained[rows] = mask & (graph_pis > 0)[None, :]
         if loss_out is not None:
             loss_out.copy_(torch.from_numpy(f["loss"].astype(np.float32)))
         if sse_out is not None:
@@ -295,6 +310,11 @@ class OracleSharedEngine:
         state._step += 1
         state.c.beta1_power, state.c.beta2_power, state.c.step = float(st["b1p"]), float(st["b2p"]), state._step
         self._buf.zero_()
+        self._seen[:] = False
+
+    def discard_gradients(self):
+        self.grad_buffer().zero_()
+        self._seen[:] = False
 
     def fit(self, target, params, state, lists, n_iters, loss_out=None, sse_out=None):
         for _ in range(n_iters):

@@ -224,6 +224,27 @@ def _lr(cfg, name):
     return {"pis": cfg.lr_pis, "A_diagonal": cfg.lr_steer, "A_corr": cfg.lr_steer}.get(name, cfg.lr_expert)
 
 
+def judge_adam(judge, name, cfg, lr, bias, g64, dg, m0, mn, mr, vr, vn, pr, pn):
+    """The three comparisons of one tensor after one Adam step (module docstring), shared with tests/shared_step_parity.py.
+    ``g64``: the UNCLIPPED fp64 gradient, ``dg``: its error bound; ``m0``: the first-moment slots before the step; ``mn``,
+    ``vn``, ``pn``: the engine's slots and parameters after it; ``mr``, ``vr``, ``pr``: the fp32 restatement's."""
+    b1, b2, eps = float(np.float32(cfg.beta1)), float(np.float32(cfg.beta2)), float(cfg.adam_eps)
+    if cfg.grad_clip is not None:
+        g64 = np.clip(g64, -cfg.grad_clip, cfg.grad_clip)
+    m0, mn = m0.astype(np.float64), mn.astype(np.float64)
+    g = (mn - b1 * m0) / (1.0 - b1)
+    judge("grad:" + name, np.abs(g - g64), dg + 10 * 2.0 ** -24 * np.maximum(np.abs(m0), np.abs(mn)))
+    vr, vn = vr.astype(np.float64), vn.astype(np.float64)
+    judge("v:" + name, np.abs(vn - vr), (2 * np.abs(g64) * dg + dg * dg) * (1.0 - b2) + 4 * 2.0 ** -24 * np.abs(vr) + 1e-37)
+    pr = pr.astype(np.float64)
+    rv = np.sqrt(vr)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        second = np.abs(mr.astype(np.float64)) * (1.0 - b2) * np.abs(g64) * dg / (rv * (rv + eps) ** 2)
+    second = np.where(rv > 0, second, 0.0)
+    tol = 1e-6 * (np.abs(pr) + 1.0) + 2e-5 * lr + lr * bias * ((1.0 - b1) * dg / (rv + eps) + second)
+    judge("param:" + name, np.abs(pn.astype(np.float64) - pr), tol)
+
+
 def check_step(eng, s, eng0=None):
     """Load ``s`` into ``eng``, run ONE fit iteration and compare with the restatement (module docstring).  ``eng0``: an engine
     of the same configuration and tiling with every learning rate 0, for the proof that the fit kernel's lattice is the
@@ -304,7 +325,6 @@ def check_step(eng, s, eng0=None):
     ratios["list"] = float((new[c] != ref["active_new"][c]).sum())
 
     m1, v1, got = _host(st.m), _host(st.v), _host(dp)
-    b1, b2, eps = float(np.float32(cfg.beta1)), float(np.float32(cfg.beta2)), float(cfg.adam_eps)
     bias = np.sqrt(1.0 - float(s.b2p)) / (1.0 - float(s.b1p))
     for name in o.PARAM_NAMES:
         lr = _lr(cfg, name)
@@ -318,23 +338,8 @@ def check_step(eng, s, eng0=None):
         # (with grad_clip the kernel clips a gradient whose rounding error is that of the UNCLIPPED tensor: its scale, as in
         # test_fit_with_loss_weights_regularisers_and_clipping)
         scale = float(np.abs(g64).max()) + 1e-30 if g64.size else 1e-30
-        if cfg.grad_clip is not None:
-            g64 = np.clip(g64, -cfg.grad_clip, cfg.grad_clip)
-        m0 = s.m[name].astype(np.float64)[c]
-        mn = m1[name].astype(np.float64)[c]
-        g = (mn - b1 * m0) / (1.0 - b1)
-        dg = 2e-5 * scale
-        judge("grad:" + name, np.abs(g - g64), dg + 10 * 2.0 ** -24 * np.maximum(np.abs(m0), np.abs(mn)))
-        vr = ast["v"][name].astype(np.float64)[c]
-        vn = v1[name].astype(np.float64)[c]
-        judge("v:" + name, np.abs(vn - vr), (2 * np.abs(g64) * dg + dg * dg) * (1.0 - b2) + 4 * 2.0 ** -24 * np.abs(vr) + 1e-37)
-        pr = p_ref[name].astype(np.float64)[c]
-        rv = np.sqrt(vr)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            second = np.abs(ast["m"][name].astype(np.float64)[c]) * (1.0 - b2) * np.abs(g64) * dg / (rv * (rv + eps) ** 2)
-        second = np.where(rv > 0, second, 0.0)
-        tol = 1e-6 * (np.abs(pr) + 1.0) + 2e-5 * lr + lr * bias * ((1.0 - b1) * dg / (rv + eps) + second)
-        judge("param:" + name, np.abs(got[name].astype(np.float64)[c] - pr), tol)
+        judge_adam(judge, name, cfg, lr, bias, g64, 2e-5 * scale, s.m[name][c], m1[name][c], ast["m"][name][c], ast["v"][name][c],
+                   v1[name][c], p_ref[name][c], got[name][c])
     return Result(ratios=ratios, failures=fails, clean=int(c.sum()), blocks=B, variant=variant, dropped=dropped)
 
 
@@ -347,5 +352,5 @@ def worst(ratios):
     return out
 
 
-__all__ = ["SHAPES", "KINDS", "OPTION_LEGS", "QKW", "build_state", "check_step", "engine_kwargs", "load_state", "worst",
+__all__ = ["SHAPES", "KINDS", "OPTION_LEGS", "QKW", "build_state", "check_step", "engine_kwargs", "judge_adam", "load_state", "worst",
            "blocks_for", "WARMUP", "LATE"]
