@@ -278,6 +278,46 @@ int smoe_render_view(smoe_handle h, const smoe_params* p, const uint32_t* active
                      const float* const axis_coords[3], const float blend[3], void* image, int32_t image_format,
                      uint8_t* argmax, void* stream);
 
+/* Point decode: the model's value at num_points arbitrary positions that owe nothing to each other -- a rotated or warped
+ * view, a motion-compensated lookup, a profile along a line, a set of probes.
+ *   points                   DEVICE [num_points, dim] fp32, source pixels in the image's axis order (y, x[, t]); pixel q covers
+ *                            [q, q + 1) (the convention of blocks.view_axis)
+ *   grid, length             blocks per axis; the true extent of the image in pixels, 1 <= length[l] <= grid[l] * block_shape[l]
+ *   p, active                cover ALL prod(grid) blocks, indexed by the image-wide block index, as does the centre grid of
+ *                            smoe_set_center_grid
+ *   values                   [num_points, C], SMOE_IMAGE_F32 (lattice values) or SMOE_IMAGE_U8 (lattice indices)
+ *   argmax                   [num_points] or NULL: uint8 local kernel id of the own block, 255 = none
+ *   block                    [num_points] or NULL: int32 image-wide index of the own block, -1 = outside
+ * Per axis l, with n = block_shape[l] and x the point's coordinate, all in IEEE fp32:
+ *   outside                  x is NaN, x < 0 or x >= length[l] on ANY axis: values 0 (U8: 0), argmax 255, block -1, nothing
+ *                            else is computed for the point
+ *   block                    the integer g with g n <= x < (g + 1) n exactly: floorf(x / n), corrected by +-1 against the
+ *                            products g n and (g + 1) n, which are exact in fp32 -- ownership does not depend on how the
+ *                            division rounds
+ *   block-unit coordinate    t = x - g n (exact), u = (t - 0.5f) / (float)(n - 1): one rounding in the subtraction, a
+ *                            correctly rounded division; u = 0 for n == 1.  On a pixel centre q + 0.5 this is entry q of
+ *                            smoe_render's training lattice linspace(0, 1, n), bit for bit
+ * The own block (image-wide index row-major over grid[]) is evaluated at (u_0, ...) exactly as smoe_render evaluates a sample of
+ * that block for prod(grid) blocks: the same active rule, fake quantisation, centre grid and hoisting level.  With blend (NULL,
+ * or per-axis half-widths with the checks and the meaning of smoe_render_blend) the sample is cross-faded with the neighbouring
+ * blocks exactly as smoe_render_blend / smoe_render_view do it: the window from u, neighbour coordinates u -+ n / (n - 1),
+ * weight 0 for neighbours outside the block grid, blocks without influence dropped, neighbours evaluated without hoisting, one
+ * rounding onto the lattice.  argmax is the own block's.  The result for a point depends on its coordinates and the model
+ * only: not on num_points, its place in the list, the other points or how the launch is cut.  So the pixel centres of the
+ * image as points are bit-identical to smoe_render / smoe_render_blend on the training lattice.
+ * A workgroup takes 1024 consecutive points; where the blocks between the per-axis minimum and maximum of their block indices
+ * (with blend: widened by one) fit the record budget -- 12 KB of derived records, at most prod(grid) -- it derives them once
+ * into LDS, otherwise every lane derives its point's block from global memory; both give the same bits.  Environment
+ * SMOE_SAMPLE_RECORDS=n (tuning / test hook) caps the records a workgroup stages; 0: never stage.  Offsets are 64-bit;
+ * stores are 16 bytes wide where values / argmax / block are 16-byte aligned, element-wise at ragged heads and tails.
+ * num_points == 0 is a successful no-op.  SMOE_ERR_INVALID names the offending argument: a null handle, p, grid, length, or
+ * (num_points > 0) points / values; grid[l] < 1; length[l] outside 1 .. grid[l] * block_shape[l]; an unknown image_format;
+ * num_points < 0; blend as in smoe_render_blend.  SMOE_ERR_UNSUPPORTED: grid[l] * block_shape[l] > 2^24 (block origins must
+ * be exact in fp32), SMOE_IMAGE_U8 with precision > 8, 2^31 or more workgroups. */
+int smoe_sample(smoe_handle h, const smoe_params* p, const uint32_t* active, const int32_t grid[3],
+                const int32_t length[3], const float* points, int64_t num_points, const float blend[3],
+                void* values, int32_t image_format, uint8_t* argmax, int32_t* block, void* stream);
+
 /* Name of the kernel variant smoe_fit would launch for num_blocks (diagnostics / profiles). */
 const char* smoe_fit_variant(smoe_handle h, int32_t num_blocks);
 

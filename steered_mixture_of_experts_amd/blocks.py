@@ -149,6 +149,56 @@ def view_axis(n: int, grid_l: int, length_l, lo, hi, E: int):
     return first, blocks, start, coords
 
 
+def point_blocks(points, block_shape: Sequence[int], grid: Sequence[int], length: Sequence[int]):
+    """Where arbitrary positions fall (``Smoe.sample``, include/smoe_hip.h: smoe_sample) -- the one host statement of the
+    mapping, in float32 throughout, as the kernel computes it.  ``points`` ``[..., d]`` in source pixels, axis order of the
+    image; pixel ``q`` covers ``[q, q + 1)``; ``length[l]`` the true extent (``1 <= length[l] <= grid[l] * n_l``).  A point is
+    outside if on any axis ``x`` is NaN, ``x < 0`` or ``x >= length[l]``.  Per axis the block is the integer ``g`` with
+    ``g n <= x < (g + 1) n`` exactly (``floor(x / n)`` corrected by +-1 against the products, which are exact in float32 for
+    ``grid[l] * n <= 2^24``), and the block-unit coordinate ``u = ((x - g n) - 0.5) / (n - 1)`` (0 for ``n == 1``): an exact
+    subtraction, one rounded subtraction, one rounded division.  Returns ``(inside [...] bool, block [..., d] int64 (0 where
+    outside), u [..., d] float32 (0 where outside))``."""
+    pts = np.asarray(points, dtype=np.float32)
+    d = len(block_shape)
+    if pts.ndim < 1 or pts.shape[-1] != d or len(grid) != d or len(length) != d:
+        raise ValueError(f"point_blocks: points need a trailing axis of {d}, grid and length {d} entries")
+    for n, g, ln in zip(block_shape, grid, length):
+        if int(n) < 1 or int(g) < 1 or not (1 <= int(ln) <= int(g) * int(n)) or int(g) * int(n) > 2 ** 24:
+            raise ValueError("point_blocks: need n, grid >= 1, 1 <= length <= grid * n <= 2^24")
+    inside = np.ones(pts.shape[:-1], dtype=bool)
+    block = np.zeros(pts.shape, dtype=np.int64)
+    u = np.zeros(pts.shape, dtype=np.float32)
+    with np.errstate(invalid="ignore"):
+        for l in range(d):
+            inside &= (pts[..., l] >= np.float32(0)) & (pts[..., l] < np.float32(int(length[l])))
+        for l in range(d):
+            n = int(block_shape[l])
+            x = np.where(inside, pts[..., l], np.float32(0)).astype(np.float32)
+            g = np.floor(x / np.float32(n)).astype(np.int64)
+            g = g - ((g * n).astype(np.float32) > x)
+            g = g + (((g + 1) * n).astype(np.float32) <= x)
+            t = x - (g * n).astype(np.float32)
+            block[..., l] = g
+            if n > 1:
+                u[..., l] = np.where(inside, (t - np.float32(0.5)) / np.float32(n - 1), np.float32(0))
+    return inside, block, u
+
+
+def warp_points(matrix, size: Sequence[int]) -> np.ndarray:
+    """The source positions of an affine view (``Smoe.render_warp``): output index ``i`` has its cell centre at ``i + 0.5`` and
+    its source position is ``x = M (i + 0.5) + t`` for ``matrix = [M | t]`` of shape ``[d, d + 1]``, in source pixels
+    (``point_blocks``' convention).  Computed in float64, rounded to float32 once.  Returns ``[*size, d]``."""
+    A = np.asarray(matrix, dtype=np.float64)
+    size = [int(v) for v in np.atleast_1d(size)]
+    d = len(size)
+    if A.shape != (d, d + 1) or not np.isfinite(A).all():
+        raise ValueError(f"warp_points: matrix must be a finite [{d}, {d + 1}] array [M | t]")
+    if min(size) < 1:
+        raise ValueError("warp_points: size needs entries >= 1")
+    idx = np.stack(np.meshgrid(*[np.arange(e, dtype=np.float64) + 0.5 for e in size], indexing="ij"), axis=-1)
+    return (idx @ A[:, :d].T + A[:, d]).astype(np.float32)
+
+
 def to_planar(blocks: np.ndarray) -> np.ndarray:
     """(B, *block_shape, C) -> (B, C, N): the C-ABI target layout (include/smoe_hip.h)."""
     B, C = blocks.shape[0], blocks.shape[-1]

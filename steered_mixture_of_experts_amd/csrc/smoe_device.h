@@ -189,6 +189,21 @@ struct ViewPlan {
     std::vector<int32_t> tab;
 };
 
+// smoe_sample (smoe_sample.hip.h): the model at a list of arbitrary positions.  r.p / r.active / r.mus_grid cover ALL
+// prod(grid) blocks (image-wide block index); r.image: the values [N, C]; r.argmax: [N] or null; r.off_par / r.off_stage: the
+// staged records / the staging buffers.  The launcher fills rec_cap and the offsets.
+struct SampleArgs {
+    RenderArgs r;
+    float s0[SMOE_MAX_DIM], s1[SMOE_MAX_DIM], band[SMOE_MAX_DIM], pitch[SMOE_MAX_DIM];   // as in RenderBlendArgs; band 0: no blend on the axis
+    const float* points;      // [N, D] source pixels
+    long long num_points;
+    int32_t* block;           // [N] image-wide index of the own block (-1: outside) or null
+    int vec_blk;              // block's base is 16-byte aligned: vector stores
+    int n[SMOE_MAX_DIM];      // pixels per block and axis
+    float length[SMOE_MAX_DIM];      // true extent of the image in pixels
+    int rec_cap;              // a workgroup stages the records of its box when the box has at most this many blocks
+};
+
 // What the launcher of a block decoder derives from checked arguments, next to the geometry fields of RenderArgs (and off_w
 // of RenderBlendArgs) it fills: a pure host computation (render_layout / render_blend_layout), also run without a device
 struct RenderLayout {
@@ -235,6 +250,10 @@ struct Variant {
     // launch of a planned view whose table is on the device
     hipError_t (*render_view_layout)(RenderViewArgs&, const ViewHost&, ViewPlan&, int hl, RenderLayout&);
     hipError_t (*render_view)(const RenderViewArgs&, const RenderLayout&, hipStream_t);
+    // point decoder (smoe_sample.hip.h): the geometry of a call (pure host code; records: the caller's cap on the staged records,
+    // < 0 none), and the launch of a planned call
+    hipError_t (*sample_layout)(SampleArgs&, int hl, long long records, RenderLayout&);
+    hipError_t (*sample)(const SampleArgs&, const RenderLayout&, hipStream_t);
 };
 
 // ---- shared-kernel image mode (smoe_shared.hip) ----------------------------------------------

@@ -857,16 +857,7 @@ class Smoe(_SmoeBase):
             raise NotImplementedError("this engine has no render_view()")
         dev = eng.device
         tabs = [blk.view_axis(n[l], self.grid[l], self.image.shape[l], win[l][0], win[l][1], E[l]) for l in range(d)]
-        params = self._quantized_params() if quantized else self._params
-        active = self._render_lists(quantized)
-        center = None
-        if self.world_size > 1:
-            full = lambda t: torch.from_numpy(np.ascontiguousarray(sdist.allgather_blocks(t.cpu().numpy(), self.num_blocks))).to(dev)
-            params = {k: full(v) for k, v in params.items()}
-            active = None if active is None else full(active)
-            if self._mus_grid is not None and int(self.quantization_mode) >= 2:
-                center = torch.from_numpy(np.ascontiguousarray(sdist.allgather_blocks(self._mus_grid, self.num_blocks),
-                                                               dtype=np.float32)).to(dev)
+        params, active, center = self._whole_model(quantized)
         res = eng.render_view(params, active, self.grid, [t[0] for t in tabs], [t[2] for t in tabs],
                               [torch.from_numpy(t[3]).to(dev) for t in tabs], blend=bl if any(v > 0 for v in bl) else None,
                               dtype=tdt, want_argmax=want_argmax, center_grid=center)
@@ -882,6 +873,74 @@ class Smoe(_SmoeBase):
             img = img.cpu().numpy()
             ids = None if ids is None else ids.cpu().numpy()
         return (img, ids) if want_argmax else img
+
+    def _whole_model(self, quantized):
+        """Parameters, kernel lists (``render``'s) and centre grid of ALL blocks on this rank's device, as ``render_view`` and
+        ``sample`` hand them to the engine: with several ranks everyone's are gathered (small: a few hundred bytes per block)."""
+        dev = self._engine.device
+        params = self._quantized_params() if quantized else self._params
+        active = self._render_lists(quantized)
+        center = None
+        if self.world_size > 1:
+            full = lambda t: torch.from_numpy(np.ascontiguousarray(sdist.allgather_blocks(t.cpu().numpy(), self.num_blocks))).to(dev)
+            params = {k: full(v) for k, v in params.items()}
+            active = None if active is None else full(active)
+            if self._mus_grid is not None and int(self.quantization_mode) >= 2:
+                center = torch.from_numpy(np.ascontiguousarray(sdist.allgather_blocks(self._mus_grid, self.num_blocks),
+                                                               dtype=np.float32)).to(dev)
+        return params, active, center
+
+    def sample(self, points, dtype=np.float32, quantized=False, want_argmax=False, to_host=True, blend=0.0):
+        """The model's value at arbitrary positions, on the device (the engine's ``sample``; include/smoe_hip.h: smoe_sample):
+        a rotated or warped view, a motion-compensated lookup, a profile along a line, a few thousand probes -- no pixel is
+        interpolated.  ``points``: array-like or a device tensor ``[..., d]`` of float32 positions in source pixels, in the
+        image's axis order (pixel ``q`` covers ``[q, q + 1)``; ``blocks.point_blocks`` is the mapping).  Returns ``[..., C]``;
+        a position outside the image (NaN, ``< 0`` or ``>= image.shape[l]`` on any axis) gives 0.  ``dtype``, ``quantized``,
+        ``blend`` and the kernel lists are ``render_view``'s; with ``want_argmax`` also the global kernel ids ``[...]``
+        (int64; -1: no kernel has influence, or outside).  The pixel centres ``q + 0.5`` give ``render()`` bit for bit.
+        ``to_host=False`` returns device tensors.  Several ranks: parameters and lists are gathered and every rank evaluates
+        all points; the result is the same on every rank and for every number of ranks."""
+        d, n = self.dim_domain, self.batch_size_valued
+        bl = [float(v) for v in np.atleast_1d(blend)]
+        bl = bl * d if len(bl) == 1 else bl
+        if len(bl) != d:
+            raise ValueError(f"sample: blend needs one value or {d}")
+        for v, nl in zip(bl, n):
+            if not np.isfinite(v) or v < 0 or v > nl / 2:
+                raise ValueError("sample: blend must lie within 0 .. block size / 2 on every axis")
+        npdt = np.dtype(dtype)
+        if npdt not in (np.dtype(np.float32), np.dtype(np.uint8)):
+            raise ValueError("sample: dtype must be float32 or uint8")
+        tdt = torch.uint8 if npdt == np.dtype(np.uint8) else torch.float32
+        eng = self._engine
+        if not hasattr(eng, "sample"):
+            raise NotImplementedError("this engine has no sample()")
+        dev = eng.device
+        pts = points if torch.is_tensor(points) else torch.from_numpy(np.ascontiguousarray(np.asarray(points), dtype=np.float32))
+        if pts.dim() < 1 or pts.shape[-1] != d:
+            raise ValueError(f"sample: points need a trailing axis of {d} coordinates")
+        lead = tuple(pts.shape[:-1])
+        pts = pts.to(device=dev, dtype=torch.float32).reshape(-1, d).contiguous()
+        params, active, center = self._whole_model(quantized)
+        res = eng.sample(params, active, self.grid, [int(v) for v in self.image.shape[:d]], pts,
+                         blend=bl if any(v > 0 for v in bl) else None, dtype=tdt, want_argmax=want_argmax,
+                         want_block=want_argmax, center_grid=center)
+        img, ids = (res[0], res[1:]) if want_argmax else (res, None)
+        img = img.reshape(lead + (self.channels,))
+        if ids is not None:
+            am, bid = ids[0].to(torch.int64), ids[1].to(torch.int64)
+            ids = self._global_ids(am, bid, bid >= 0).reshape(lead)
+        if to_host:
+            img = img.cpu().numpy()
+            ids = None if ids is None else ids.cpu().numpy()
+        return (img, ids) if want_argmax else img
+
+    def render_warp(self, matrix, size, **options):
+        """An affine view of the model: ``sample(blocks.warp_points(matrix, size), **options)``.  ``matrix = [M | t]``
+        ``[d, d + 1]`` maps the cell centre ``i + 0.5`` of output index ``i`` to the source position ``M (i + 0.5) + t`` in
+        source pixels -- a rotation, a shear, any zoom.  Returns the image ``[*size, C]`` (0 where the view leaves the image);
+        ``options`` are ``sample``'s."""
+        return self.sample(blk.warp_points(matrix, size), **options)
 
     # hooks of _render
     def _engine_render_blend(self, params, active, axes, grid, extent, out, tdt, want_argmax, blend):

@@ -11,6 +11,9 @@ pixels of every block border (``Smoe.render(blend=...)``): no block seams in the
 ``--window LO HI ...`` (two numbers per axis, source pixels) and / or ``--size E ...`` (output samples per axis) decode a
 viewport with ``Smoe.render_view``: only that window of the image, at that size (``--size`` absent: ``--scale`` times the
 window; ``--window`` absent: the whole image); they work together with ``--scale`` and ``--blend``; per-block models only.
+``--affine M.. T..`` (``d (d + 1)`` numbers, row-major ``[M | t]``) with ``--size`` decodes an affine view with
+``Smoe.render_warp``: output cell centre ``i + 0.5`` shows the source position ``M (i + 0.5) + t`` (source pixels), a rotation
+or a shear included; it works with ``--blend``, not with ``--window`` / ``--frames`` / ``--scale``; per-block models only.
 """
 import argparse
 import os
@@ -43,7 +46,7 @@ _shared_engine_factory = None      # tests put the oracle-backed engine here; No
 
 
 def main(image_path, results_path, params_file, batches=1, bit_depths=(20, 18, 6, 10, 10), quant_params=False,
-         scale=None, frames=None, blend=None, window=None, size=None):
+         scale=None, frames=None, blend=None, window=None, size=None, affine=None):
     if len(bit_depths) != 5:
         raise ValueError("Number of bit depths must be five!")           # smoe_reconstruction.py:17-18
     orig, precision, _ = read_image(image_path)
@@ -87,7 +90,26 @@ def main(image_path, results_path, params_file, batches=1, bit_depths=(20, 18, 6
         reconstruction = smoe.get_reconstruction()
     sc = [float(v) for v in np.atleast_1d(1.0 if scale is None else scale)]
     bl = [float(v) for v in np.atleast_1d(0.0 if blend is None else blend)]
-    if window is not None or size is not None:
+    if affine is not None:
+        # an affine view: every output sample at its own source position (Smoe.render_warp)
+        if not hasattr(smoe, "render_warp"):
+            raise ValueError("--affine needs a per-block model: this pickle holds a whole-image (shared-kernel) model, which "
+                             "has no point decoder")
+        d = smoe.dim_domain
+        if size is None:
+            raise ValueError("--affine needs --size (the output samples per axis)")
+        if window is not None or frames is not None or scale is not None:
+            raise ValueError("--affine does not go with --window / --frames / --scale (the matrix holds them)")
+        if len(affine) != d * (d + 1):
+            raise ValueError(f"--affine takes {d * (d + 1)} numbers: the rows of [M | t]")
+        if len(size) != d:
+            raise ValueError(f"--size takes one number per axis ({d})")
+        reconstruction = smoe.render_warp(np.asarray(affine, dtype=np.float64).reshape(d, d + 1), [int(v) for v in size],
+                                          quantized=with_q, blend=bl)
+        reconstruction_path += "_warp" + "x".join(str(v) for v in reconstruction.shape[:d])
+        if any(v != 0.0 for v in bl):
+            reconstruction_path += "_blend" + "x".join("%g" % v for v in bl)
+    elif window is not None or size is not None:
         # a viewport: that window of the image at that size and nothing else (Smoe.render_view)
         if not hasattr(smoe, "render_view"):
             raise ValueError("--window / --size need a per-block model: this pickle holds a whole-image (shared-kernel) "
@@ -147,6 +169,9 @@ def _parser():
                         help="decode only this window of the image: LO HI per axis, in source pixels (per-block models only)")
     parser.add_argument('--size', type=int, default=None, nargs='+',
                         help="output samples per axis of the window (default: --scale times the window)")
+    parser.add_argument('--affine', type=float, default=None, nargs='+',
+                        help="decode an affine view of --size samples: the d (d + 1) numbers of [M | t], row-major; output "
+                             "cell centre i + 0.5 shows source position M (i + 0.5) + t (per-block models only)")
     return parser
 
 
