@@ -454,6 +454,62 @@ int smoe_shared_render(smoe_shared_handle h, int32_t first_batch, int32_t num_ba
                        const uint32_t* lists, const float* const axis_coords[3], const int32_t samples[3],
                        void* image, int32_t image_format, int32_t* argmax, void* stream);
 
+/* Point decoder of the shared-kernel mode: the whole-image model at num_points arbitrary positions, into the dense
+ * [num_points, C] -- the counterpart of smoe_sample: a rotated or stabilised view, a profile, a few thousand probes.
+ *   p                        the global kernels; fake quantisation (quantize_pis, mode 2, mode 3 with the IMAGE-wide ranges of
+ *                            THIS call's parameters) and the centre grid exactly as in smoe_shared_render
+ *   lists                    [num_batches, KW] bitmaps of ALL batches of the handle, indexed by the global batch id, only
+ *                            read; NULL = every kernel, for every point
+ *   points                   DEVICE [num_points, dim] fp32 positions in source pixels, image axis order; pixel q covers
+ *                            [q, q + 1)
+ *   values                   [num_points, C], SMOE_IMAGE_F32 (lattice values) or SMOE_IMAGE_U8 (lattice indices)
+ *   argmax                   [num_points] int32 or NULL: GLOBAL kernel id of the first maximum among the kernels with
+ *                            influence on the point, -1 where none has, or outside
+ * Per axis l, with nb = batch_shape[l], S = image_shape[l] and x the point's coordinate, all in IEEE fp32:
+ *   outside                  x is NaN, x < 0 or x >= S on ANY axis: values 0 (U8: 0), argmax -1, nothing else is computed
+ *   owning batch             the integer g with g nb <= x < (g + 1) nb exactly: floorf(x / nb), corrected by +-1 against the
+ *                            products g nb and (g + 1) nb, which are exact in fp32 -- ownership does not depend on how the
+ *                            division rounds.  A point on a batch boundary g nb belongs to batch g
+ *   image-unit coordinate    u = (x - 0.5f) / (float)(S - 1): one rounded subtraction, a correctly rounded division; u = 0
+ *                            for S == 1.  On a pixel centre q + 0.5 this is entry q of the training lattice
+ *                            linspace(0, 1, S), bit for bit
+ * The point is evaluated at (u_0, ...) with the list of its batch exactly as smoe_shared_render evaluates a sample of that
+ * batch: the same compacted list (listed and fake-quantised prior > 0, ascending ids), records, sweeps and lattice stage.  Its
+ * result depends on its coordinates, the model and its batch's list only -- not on num_points, its place in the list, the
+ * other points or how the launch is cut.  So the pixel centres as points are bit-identical to smoe_shared_render on the
+ * training lattice (and to the recon of smoe_shared_forward), the empty list gives 0 / -1.
+ * A workgroup takes 1024 consecutive points and walks the distinct batches among them in ascending order, compacting and
+ * staging one batch's list at a time (about 7 us per batch and workgroup on the MI355X): a row-major view or warp meets
+ * 1024 / (samples per batch on the innermost axis) batches per image row a workgroup covers, scattered probes up to one per
+ * point -- correct, and slow.  Offsets are 64-bit; stores are 16 bytes wide where values / argmax are 16-byte aligned,
+ * element-wise at ragged heads and tails.
+ * num_points == 0 is a successful no-op.  SMOE_ERR_INVALID names the offending argument: a null handle, p, or
+ * (num_points > 0) points / values; num_points < 0; an unknown image_format.  SMOE_ERR_UNSUPPORTED: SMOE_IMAGE_U8 with
+ * precision > 8, image_shape[l] > 2^24 (batch origins must be exact in fp32), 2^31 or more workgroups, more than 160 KB of
+ * LDS. */
+int smoe_shared_sample(smoe_shared_handle h, const smoe_params* p, const uint32_t* lists,
+                       const float* points, int64_t num_points,
+                       void* values, int32_t image_format, int32_t* argmax, void* stream);
+
+/* Viewport decoder of the shared-kernel mode: a dense view [E_0, E_1(, E_2), C] of the whole-image model given by per-axis
+ * tables -- the counterpart of smoe_render_view: only the view is computed and stored (an 8x detail, a thumbnail, one frame).
+ *   p, lists                 as in smoe_shared_sample (lists of ALL batches, global batch id; NULL = every kernel)
+ *   extent[l]                E_l >= 1 samples on axis l; the image is row-major over extent
+ *   axis_coords[l]           DEVICE table of E_l fp32 coordinates in image units (as in smoe_shared_render)
+ *   axis_batch[l]            DEVICE table of E_l int32 batch indices on axis l, 0 <= . < grid_l (a value outside is clamped
+ *                            into that range): sample (i_0, i_1, ..) is evaluated with the list of batch
+ *                            (axis_batch[0][i_0], axis_batch[1][i_1], ..) of the handle's batch grid (row-major)
+ *   image, image_format, argmax   as values / argmax of smoe_shared_sample, [E.., C] and [E..]
+ * The kernel computes neither coordinates nor ownership here and nothing is outside; a sample is evaluated exactly as
+ * smoe_shared_sample evaluates a point with these coordinates in this batch (one kernel family, the same contract), so a
+ * view whose tables are a crop of smoe_shared_render's grid is bit-identical to that crop.  Entries [dim .. 2] of the arrays
+ * are ignored.  SMOE_ERR_INVALID names the offending argument: a null handle, p, extent, axis_coords, axis_batch, image or
+ * table; extent[l] < 1; an unknown image_format.  SMOE_ERR_UNSUPPORTED as in smoe_shared_sample (no limit on image_shape). */
+int smoe_shared_render_view(smoe_shared_handle h, const smoe_params* p, const uint32_t* lists,
+                            const int32_t extent[3], const float* const axis_coords[3],
+                            const int32_t* const axis_batch[3],
+                            void* image, int32_t image_format, int32_t* argmax, void* stream);
+
 /* run_batched(train=True) minus train_op: forward + tf.gradients of the batches, accumulated into
  * the handle's gradient buffer (accum_ops, smoe.py:1150); kernel lists pruned (smoe.py:1763-1766).
  * Summation order: every batch leaves the raw sums of its listed kernels in a row of its own; the buffer is the sum of

@@ -312,6 +312,30 @@ struct SharedRenderArgs {
     KernelConsts kc;
 };
 
+// smoe_shared_sample / smoe_shared_render_view (smoe_shared_sample.hip.h): the model at num_points positions, every one with
+// the list of the batch that owns it.  Either the list `points` (source pixels; batch and coordinate made by the kernel) or
+// the dense row-major view of `ext` with one coordinate table ax[l] and one batch-index table ab[l] per axis.
+struct SharedSampleArgs {
+    smoe_params p;            // global kernels [K,...]
+    const uint32_t* lists;    // [num_batches][KW] bitmaps of ALL batches (global batch id), only read; null = every kernel
+    const float* points;      // [N, D] source pixels (list mode)
+    long long num_points;     // N, or prod(ext)
+    const float* ax[SMOE_MAX_DIM];    // view mode: [ext_l] coordinates in image units
+    const int32_t* ab[SMOE_MAX_DIM];  // view mode: [ext_l] batch index on the axis
+    int ext[SMOE_MAX_DIM];    // view mode: samples per axis
+    int nbs[SMOE_MAX_DIM];    // batch_shape
+    int grid[SMOE_MAX_DIM];   // batches per axis
+    int shape[SMOE_MAX_DIM];  // image_shape
+    int K, KW;
+    void* image;              // [N, C] float32 or uint8
+    int fmt;                  // SMOE_IMAGE_F32 / SMOE_IMAGE_U8
+    int32_t* argmax;          // [N] global kernel ids, -1 = no kernel has influence, or outside; or null
+    int vec_img, vec_arg;     // the plane's base is 16-byte aligned: vector stores
+    const float* qrng;        // as in SharedArgs
+    const float* mus_grid;    // as in SharedArgs
+    KernelConsts kc;
+};
+
 // Per-kernel sum over the batches of the current pass, in a fixed order (lane = batch mod 64 ascending, then a butterfly
 // over the lanes): racc[k][PK] and nact[k] are OVERWRITTEN -- bit-identical from run to run and for every split of the
 // batches of a rank over smoe_shared_accumulate calls.
@@ -388,6 +412,11 @@ hipError_t launch_shared_ranges(const SharedRangesArgs& a, int D, int C, hipStre
 // split_hint > 0: workgroups per batch (test / tuning hook); 0: chosen from nb and num_cus.  hipErrorNotSupported: more than
 // 2^30 samples per batch
 hipError_t launch_shared_render(const SharedRenderArgs& a, int D, int C, int num_cus, int split_hint, hipStream_t st);
+// the geometry of a smoe_shared_sample / smoe_shared_render_view call (pure host code; g.hl is unused and 0).
+// hipErrorNotSupported: 2^31 or more workgroups, or more than 160 KB of LDS
+hipError_t shared_sample_layout(int D, int C, int K, long long num_points, RenderLayout& g);
+// the launch of a planned call; grid: the dense view of a.ext / a.ax / a.ab instead of the list a.points
+hipError_t launch_shared_sample(const SharedSampleArgs& a, int D, int C, bool grid, const RenderLayout& g, hipStream_t st);
 
 const Variant* variants(int* count);
 hipError_t launch_readmit(const ReadmitArgs& a, int D, hipStream_t st);

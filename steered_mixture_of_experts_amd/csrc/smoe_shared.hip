@@ -1142,6 +1142,8 @@ __global__ void shared_readmit_kernel(SharedReadmitArgs a) {
 
 // the decoder of this mode (shared_render_kernel, launch_shared_render)
 #include "smoe_shared_render.hip.h"
+// its point and viewport decoder (shared_sample_kernel, launch_shared_sample)
+#include "smoe_shared_sample.hip.h"
 
 namespace smoe {
 

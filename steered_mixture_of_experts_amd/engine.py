@@ -634,6 +634,66 @@ class SharedEngine(_Engine):
                                                    _slots(C.c_int32, samples, 1), _ptr(out), fmt, _ptr(am), self._stream()))
         return (out, am) if want_argmax else out
 
+    def _check_all_lists(self, who, lists):
+        """``lists`` of ALL batches, as the point and viewport decoders index them (global batch id), or None."""
+        want = (self.num_batches, self.list_words)
+        if lists is not None and (tuple(lists.shape) != want or lists.dtype != torch.int32 or not lists.is_contiguous()
+                                  or lists.device != self.device):
+            raise ValueError(f"{who}: lists must be a contiguous int32 {list(want)} tensor on {self.device} (all batches)")
+
+    def _dense_planes(self, who, shape, out, dtype, want_argmax):
+        """The value plane ``[*shape, C]`` (``out`` checked, or a new one), its format constant and the id plane or None."""
+        if dtype not in (torch.float32, torch.uint8):
+            raise ValueError(f"{who}: dtype must be torch.float32 or torch.uint8")
+        full = tuple(shape) + (self.cfg.channels,)
+        if out is None:
+            out = torch.empty(full, dtype=dtype, device=self.device)
+        elif tuple(out.shape) != full or out.dtype != dtype or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"{who}: out must be a contiguous {dtype} tensor {full} on {self.device}")
+        am = torch.empty(tuple(shape), dtype=torch.int32, device=self.device) if want_argmax else None
+        return out, (_lib.SMOE_IMAGE_U8 if dtype == torch.uint8 else _lib.SMOE_IMAGE_F32), am
+
+    def sample(self, params, lists, points, out=None, dtype=torch.float32, want_argmax=False):
+        """Point decode (include/smoe_hip.h: smoe_shared_sample): the model at the positions ``points`` -- a contiguous float32
+        device tensor ``[N, d]`` in source pixels (``blocks.point_blocks`` states the mapping) -- into ``[N, C]``, every point
+        with the kernel list of the batch that owns it.  ``lists`` int32 ``[num_batches, KW]`` of ALL batches (only read) or
+        None: every kernel.  Points outside the image give 0.  Returns the values, with ``want_argmax`` also the int32 global
+        kernel ids ``[N]`` (-1: no kernel has influence, or outside)."""
+        d, who = self.cfg.dim, "sample"
+        if points.dim() != 2 or points.shape[1] != d or points.dtype != torch.float32 or not points.is_contiguous() \
+                or points.device != self.device:
+            raise ValueError(f"{who}: points must be a contiguous float32 tensor [N, {d}] on {self.device}")
+        self._check_all_lists(who, lists)
+        N = int(points.shape[0])
+        out, fmt, am = self._dense_planes(who, (N,), out, dtype, want_argmax)
+        if N > 0:
+            cp = self._cparams(params)
+            _lib.check(self.lib.smoe_shared_sample(self._h, C.byref(cp), _ptr(lists), _ptr(points), N, _ptr(out), fmt, _ptr(am),
+                                                   self._stream()))
+        return (out, am) if want_argmax else out
+
+    def render_view(self, params, lists, axes, batches, out=None, dtype=torch.float32, want_argmax=False):
+        """Viewport decode (include/smoe_hip.h: smoe_shared_render_view): the dense view ``[*E, C]`` whose axis ``l`` has the
+        ``E_l`` coordinates ``axes[l]`` (float32 device table, image units) and is evaluated with the lists of the batches
+        ``batches[l]`` (int32 device table ``[E_l]`` of batch indices on that axis, ``0 .. grid_l - 1``).  ``lists`` as in
+        ``sample``.  Returns the image, with ``want_argmax`` also the int32 global kernel ids ``[*E]`` (-1: none)."""
+        who = "render_view"
+        self._check_render_arity(who, dtype, axes, (batches,), "axes and batches")
+        self._check_axis_tables(who, axes)
+        extent = [int(t.numel()) for t in axes]
+        for l, t in enumerate(batches):
+            if t.dim() != 1 or t.dtype != torch.int32 or not t.is_contiguous() or t.device != self.device \
+                    or t.numel() != extent[l]:
+                raise ValueError(f"{who}: every batch table must be a contiguous 1-d int32 tensor on {self.device} "
+                                 f"with as many entries as its axis table ({extent})")
+        self._check_all_lists(who, lists)
+        out, fmt, am = self._dense_planes(who, extent, out, dtype, want_argmax)
+        cp = self._cparams(params)
+        _lib.check(self.lib.smoe_shared_render_view(self._h, C.byref(cp), _ptr(lists), _slots(C.c_int32, extent, 1),
+                                                    self._axis_slots(axes), self._axis_slots(batches), _ptr(out), fmt, _ptr(am),
+                                                    self._stream()))
+        return (out, am) if want_argmax else out
+
     def accumulate(self, target, params, lists, first_batch=0, loss_out=None, sse_out=None):
         nb = lists.shape[0]
         self._check_target(target, nb)

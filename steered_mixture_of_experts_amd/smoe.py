@@ -1267,6 +1267,114 @@ class SharedSmoe(_SmoeBase):
             raise ValueError("render: blend is for block models; a whole-image model has no block seams")
         return self._render(scale, samples_per_block, dtype, quantized, want_argmax, to_host, use_lists)
 
+    # -- decoding at arbitrary points and in viewports ------------------------------------------
+    # (``Smoe`` calls these sample / render_view / render_warp; here they carry names of their own.)
+    def _eval_model(self, who, dtype, quantized, use_lists, method):
+        """What the point and viewport decoders take: the torch dtype, the engine, the parameters and the kernel lists of
+        ALL batches on this rank's device (``render``'s lists; with several ranks everyone's are gathered -- the parameters
+        are replicated anyway)."""
+        npdt = np.dtype(dtype)
+        if npdt not in (np.dtype(np.float32), np.dtype(np.uint8)):
+            raise ValueError(f"{who}: dtype must be float32 or uint8")
+        tdt = torch.uint8 if npdt == np.dtype(np.uint8) else torch.float32
+        eng = self._engine
+        if not hasattr(eng, method):
+            raise NotImplementedError(f"this engine has no {method}()")
+        params = self._quantized_params() if quantized else self._params
+        lists = self._render_lists(quantized) if use_lists else None
+        if lists is not None and self.world_size > 1:
+            full = sdist.allgather_blocks(lists.cpu().numpy(), self.num_batches)
+            lists = torch.from_numpy(np.ascontiguousarray(full)).to(eng.device)
+        return tdt, eng, params, lists
+
+    @staticmethod
+    def _eval_result(res, want_argmax, to_host):
+        img, ids = res if want_argmax else (res, None)
+        ids = None if ids is None else ids.to(torch.int64)
+        if to_host:
+            img = img.cpu().numpy()
+            ids = None if ids is None else ids.cpu().numpy()
+        return (img, ids) if want_argmax else img
+
+    def eval_points(self, points, dtype=np.float32, quantized=False, want_argmax=False, to_host=True, use_lists=True):
+        """The model's value at arbitrary positions, on the device (the engine's ``sample``; include/smoe_hip.h:
+        smoe_shared_sample) -- ``Smoe.sample`` for a whole-image model: a rotated or warped view, a profile along a line, a
+        few thousand probes; no pixel is interpolated.  ``points``: array-like or a device tensor ``[..., d]`` of float32
+        positions in source pixels, in the image's axis order (pixel ``q`` covers ``[q, q + 1)``).  A point is evaluated with
+        the kernel list of the batch it lies in (``blocks.point_blocks(points, batch_size_valued, grid, image.shape)[1]``)
+        at the image-unit coordinate ``(x - 0.5) / (S - 1)`` (``blocks.point_blocks(points, image.shape, [1] * d,
+        image.shape)[2]``).  Returns ``[..., C]``; a position outside the image (NaN, ``< 0`` or ``>= image.shape[l]`` on any
+        axis) gives 0.  ``dtype``, ``quantized``, ``use_lists`` and the lists are ``render``'s; with ``want_argmax`` also the
+        global kernel ids ``[...]`` (int64; -1: no kernel has influence, or outside).  The pixel centres ``q + 0.5`` give
+        ``render()`` bit for bit.  ``to_host=False`` returns device tensors.  Several ranks: the lists are gathered and every
+        rank evaluates all points; the result is the same on every rank and for every number of ranks.
+        Neighbouring points are cheap, scattered ones are not: the device walks the distinct batches among 1024 consecutive
+        points one after the other."""
+        d = self.dim_domain
+        tdt, eng, params, lists = self._eval_model("eval_points", dtype, quantized, use_lists, "sample")
+        pts = points if torch.is_tensor(points) else torch.from_numpy(np.ascontiguousarray(np.asarray(points), dtype=np.float32))
+        if pts.dim() < 1 or pts.shape[-1] != d:
+            raise ValueError(f"eval_points: points need a trailing axis of {d} coordinates")
+        lead = tuple(pts.shape[:-1])
+        pts = pts.to(device=eng.device, dtype=torch.float32).reshape(-1, d).contiguous()
+        res = eng.sample(params, lists, pts, dtype=tdt, want_argmax=want_argmax)
+        img, ids = res if want_argmax else (res, None)
+        img = img.reshape(lead + (self.channels,))
+        ids = None if ids is None else ids.reshape(lead)
+        return self._eval_result((img, ids) if want_argmax else img, want_argmax, to_host)
+
+    def eval_view(self, window, size=None, scale=None, dtype=np.float32, quantized=False, want_argmax=False,
+                  to_host=True, use_lists=True):
+        """Decode a viewport: the axis-aligned ``window`` of the image domain at the output ``size``, on the device (the
+        engine's ``render_view``; include/smoe_hip.h: smoe_shared_render_view) -- ``Smoe.render_view`` for a whole-image
+        model.  Only the window is computed and stored: an 8x detail, a fit-to-window zoom, a thumbnail with fewer samples
+        than batches, one frame of a video.  ``window``: one ``(lo, hi)`` per axis in source pixels (pixel ``q`` covers
+        ``[q, q + 1)``, ``0 <= lo < hi <= image.shape[l]``; None for an axis, or for all: the whole axis).  ``size``: the
+        ``E_l`` output samples per axis, or ``scale`` (a number or one per axis): ``E_l = max(1, round((hi - lo) *
+        scale_l))``; not both, neither: scale 1.  Sample ``i`` sits at ``lo + (i + 0.5)(hi - lo) / E_l``: its coordinate is
+        ``blocks.view_axis(S, 1, S, lo, hi, E)[3]`` on the image axis of ``S`` pixels, its batch the one of
+        ``blocks.view_axis(n, grid_l, S, lo, hi, E)`` -- a window that is a crop of a ``render`` grid gives exactly that
+        crop.  The other options and the return value are ``eval_points``'s, ``[*E, C]``."""
+        d, n = self.dim_domain, self.batch_size_valued
+        shape = [int(v) for v in self.image.shape[:d]]
+        window = [None] * d if window is None else list(window)
+        if len(window) != d:
+            raise ValueError(f"eval_view: window needs one (lo, hi) per axis ({d})")
+        win = [(0.0, float(shape[l])) if w is None else (float(w[0]), float(w[1])) for l, w in enumerate(window)]
+        for l, (lo, hi) in enumerate(win):
+            if not (0.0 <= lo < hi <= float(shape[l])):
+                raise ValueError(f"eval_view: window[{l}] must satisfy 0 <= lo < hi <= {shape[l]}")
+        if size is not None and scale is not None:
+            raise ValueError("eval_view: give size or scale, not both")
+        if size is not None:
+            E = [int(v) for v in np.atleast_1d(size)]
+            E = E * d if len(E) == 1 else E
+            if len(E) != d or min(E) < 1:
+                raise ValueError(f"eval_view: size needs {d} entries >= 1")
+        else:
+            sc = list(np.atleast_1d(1 if scale is None else scale))
+            sc = sc * d if len(sc) == 1 else sc
+            if len(sc) != d:
+                raise ValueError(f"eval_view: scale needs one value or {d}")
+            E = [max(1, int(round((hi - lo) * float(v)))) for (lo, hi), v in zip(win, sc)]
+        tdt, eng, params, lists = self._eval_model("eval_view", dtype, quantized, use_lists, "render_view")
+        axes, batches = [], []
+        for l in range(d):
+            axes.append(blk.view_axis(shape[l], 1, shape[l], win[l][0], win[l][1], E[l])[3])
+            first, nblocks, start, _ = blk.view_axis(n[l], shape[l] // n[l], shape[l], win[l][0], win[l][1], E[l])
+            batches.append((first + np.repeat(np.arange(nblocks), np.diff(start))).astype(np.int32))
+        dev = eng.device
+        res = eng.render_view(params, lists, [torch.from_numpy(a).to(dev) for a in axes],
+                              [torch.from_numpy(b).to(dev) for b in batches], dtype=tdt, want_argmax=want_argmax)
+        return self._eval_result(res, want_argmax, to_host)
+
+    def eval_warp(self, matrix, size, **options):
+        """An affine view of the model: ``eval_points(blocks.warp_points(matrix, size), **options)`` -- ``Smoe.render_warp``
+        for a whole-image model.  ``matrix = [M | t]`` ``[d, d + 1]`` maps the cell centre ``i + 0.5`` of output index ``i``
+        to the source position ``M (i + 0.5) + t`` in source pixels.  Returns the image ``[*size, C]`` (0 where the view
+        leaves the image)."""
+        return self.eval_points(blk.warp_points(matrix, size), **options)
+
     # hooks of _render
     def _local_rparams(self):
         return {k: np.ascontiguousarray(self.rparams[k][0], dtype=np.float32) for k in PARAM_NAMES}
