@@ -318,6 +318,40 @@ int smoe_sample(smoe_handle h, const smoe_params* p, const uint32_t* active, con
                 const int32_t length[3], const float* points, int64_t num_points, const float blend[3],
                 void* values, int32_t image_format, uint8_t* argmax, int32_t* block, void* stream);
 
+/* Point derivative: the exact spatial derivative of the model at num_points arbitrary positions -- what an edge map, a
+ * structure tensor, a temporal slope dv/dt, a sub-pixel refinement or a Gauss-Newton alignment needs.  Differences of
+ * smoe_sample sit on the 8-bit lattice; this is the closed form.
+ *   points, grid, length, p, active, blend     smoe_sample's: the same outside rule, own block g and block-unit coordinate u,
+ *                            the same active rule, fake quantisation and centre grid
+ *   jac                      [num_points, dim, C] fp32: jac[i, l, c] = dV_c / dx_l per SOURCE PIXEL
+ *   values                   [num_points, C] fp32 or NULL: V, the value BEFORE the lattice (not smoe_sample's lattice value)
+ *   block                    [num_points] or NULL: int32 image-wide index of the own block, -1 = outside
+ * One block b at block-unit position u, over its evaluated kernels k (listed, pis > 0):
+ *   gate                     g_k = coef_k exp(-m_k / 2), S = sum_k g_k, w_k = g_k / max(S, 1e-11), M_k = [w_k > tau] (strict)
+ *   experts and value        e_kc = nu_kc + sum_l Gamma_klc u_l, y_c = sum_k M_k w_k e_kc, v_c = clip(y_c, 0, nudged_max)
+ *   log-gate slope           s_k = d log g_k / du = -A_k z_k with z_k = A_k^T (u - mu_k); train_inverse_cov: s_k = -A_k r_k with
+ *                            the symmetric A_k and r_k = u - mu_k
+ *   normaliser               sbar = sum_j w_j s_j over all evaluated kernels j when S > 1e-11; 0 on the floor
+ *   derivative               dy_c / du_l = sum_k M_k w_k ((s_kl - sbar_l) e_kc + Gamma_klc): the mask is piecewise constant
+ *   clip                     dv_c / du_l = dy_c / du_l where clip(y_c) == y_c, else 0 (the fit's straight-through test)
+ *   lattice                  ignored: the derivative of the value before floor(v (2^p - 1) + 1/2)
+ * Blend (windows, neighbour coordinates u -+ n / (n - 1), weight 0 outside the grid, blocks without influence dropped: all
+ * smoe_render_blend's): d|w_l| / du_l = +0.5 / b_l for the high neighbour where its ratio 0.5 (1 + (u - s1) / b) lies strictly
+ * inside (0, 1), -0.5 / b_l for the low neighbour where its ratio 0.5 (1 + (s0 - u) / b) does, 0 where the ratio is clamped or
+ * the neighbour is outside the grid; W_b is the product over the axes of |w_l| or 1 - |w_l| and dW_b follows by the product
+ * rule.  Over the blocks kept, V = sum W_b v_b / sum W_b and dV = (sum (dW_b v_b + W_b dv_b) - V sum dW_b) / sum W_b; a
+ * neighbour's dv_b / du needs no chain factor (its coordinate is u plus a constant); no block left: V = 0, dV = 0.
+ * Units: jac[i, l, c] = dV_c / du_l / (n_l - 1); 0 on an axis with n_l == 1.  Outside points: jac 0, values 0, block -1.  A
+ * point owes nothing to the other points, its place in the list or how the launch is cut.
+ * A workgroup takes 512 consecutive points; records are staged as in smoe_sample (SMOE_SAMPLE_RECORDS applies).  Offsets are
+ * 64-bit; stores are 16 bytes wide where jac / values / block are 16-byte aligned, element-wise at ragged heads and tails.
+ * num_points == 0 is a successful no-op.  SMOE_ERR_INVALID names the offending argument: a null handle, p, grid, length, or
+ * (num_points > 0) points / jac; grid[l] < 1; length[l] outside 1 .. grid[l] * block_shape[l]; num_points < 0; blend as in
+ * smoe_render_blend.  SMOE_ERR_UNSUPPORTED: grid[l] * block_shape[l] > 2^24, 2^31 or more workgroups, more than 160 KB of LDS. */
+int smoe_sample_grad(smoe_handle h, const smoe_params* p, const uint32_t* active, const int32_t grid[3],
+                     const int32_t length[3], const float* points, int64_t num_points, const float blend[3],
+                     float* jac, float* values, int32_t* block, void* stream);
+
 /* Name of the kernel variant smoe_fit would launch for num_blocks (diagnostics / profiles). */
 const char* smoe_fit_variant(smoe_handle h, int32_t num_blocks);
 

@@ -31,7 +31,7 @@ EXPORTS = (
     "smoe_shared_fit", "smoe_shared_update_kernel_list", "smoe_shared_set_loss_weights",
     "smoe_set_center_grid", "smoe_shared_set_center_grid", "smoe_set_total_blocks", "smoe_padded_kernels_full", "smoe_shared_discard", "smoe_set_sampling",
     "smoe_render", "smoe_shared_render", "smoe_last_fit_variant", "smoe_render_blend",
-    "smoe_render_view", "smoe_sample", "smoe_shared_sample", "smoe_shared_render_view",
+    "smoe_render_view", "smoe_sample", "smoe_shared_sample", "smoe_shared_render_view", "smoe_sample_grad",
 )
 
 
@@ -117,6 +117,8 @@ def load() -> C.CDLL:
                                      fp, i32, fp, vp]
     lib.smoe_sample.argtypes = [vp, C.POINTER(SmoeParams), fp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), fp, C.c_int64,
                                 C.POINTER(C.c_float), fp, i32, fp, fp, vp]
+    lib.smoe_sample_grad.argtypes = [vp, C.POINTER(SmoeParams), fp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), fp, C.c_int64,
+                                     C.POINTER(C.c_float), fp, fp, fp, vp]
     lib.smoe_fit_variant.argtypes = [vp, i32]
     lib.smoe_fit_variant.restype = C.c_char_p
     lib.smoe_last_fit_variant.argtypes = [vp]

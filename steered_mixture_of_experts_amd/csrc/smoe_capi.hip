@@ -1124,6 +1124,91 @@ int smoe_sample(smoe_handle h, const smoe_params* p, const uint32_t* active, con
 #endif
 }
 
+int smoe_sample_grad(smoe_handle h, const smoe_params* p, const uint32_t* active, const int32_t grid[3],
+                     const int32_t length[3], const float* points, int64_t num_points, const float blend[3],
+                     float* jac, float* values, int32_t* block, void* stream) {
+    const std::string fn = "smoe_sample_grad";
+    if (!h) return fail(SMOE_ERR_INVALID, fn + ": null handle");
+    if (!params_ok(p)) return fail(SMOE_ERR_INVALID, fn + ": p (all six parameter tensors) is required");
+    if (!grid) return fail(SMOE_ERR_INVALID, fn + ": grid is required");
+    if (!length) return fail(SMOE_ERR_INVALID, fn + ": length is required");
+    if (num_points < 0) return fail(SMOE_ERR_INVALID, fn + ": num_points must be >= 0");
+    const int D = h->cfg.dim;
+    long long total = 1;
+    bool exact = true;
+    for (int l = 0; l < D; ++l) {
+        const std::string ax = "[" + std::to_string(l) + "]";
+        const long long n = h->cfg.block_shape[l];
+        if (grid[l] < 1) return fail(SMOE_ERR_INVALID, fn + ": grid" + ax + " must be >= 1");
+        total *= grid[l];
+        if (total > 0x7fffffffLL) return fail(SMOE_ERR_INVALID, fn + ": grid has more than 2^31 blocks");
+        if (length[l] < 1 || length[l] > grid[l] * n)
+            return fail(SMOE_ERR_INVALID, fn + ": length" + ax + " must be 1 .. grid * block_shape");
+        exact = exact && grid[l] * n <= (1LL << 24);
+    }
+    bool any = false;
+    if (blend) {
+        for (int l = 0; l < D; ++l) {
+            const int n = h->cfg.block_shape[l];
+            if (!std::isfinite(blend[l]) || blend[l] < 0.0f || blend[l] > 0.5f * (float)n)
+                return fail(SMOE_ERR_INVALID, fn + ": blend[" + std::to_string(l) + "] must be finite and within 0 .. block_shape / 2");
+            any = any || (blend[l] > 0.0f && n > 1);
+        }
+    }
+    if (num_points == 0) return SMOE_OK;
+    if (!points) return fail(SMOE_ERR_INVALID, fn + ": points is required");
+    if (!jac) return fail(SMOE_ERR_INVALID, fn + ": jac is required");
+    if (!exact) return fail(SMOE_ERR_UNSUPPORTED, fn + ": grid * block_shape must not exceed 2^24 on any axis (block origins are exact in fp32)");
+
+    // the kernel lists, the fake quantisation and the centre grid of a decode of the whole image: the variant of prod(grid) blocks
+    const smoe::Variant* v = nullptr;
+    int hl = 0;
+    const int rp = render_plan(h, fn.c_str(), (int32_t)total, &v, &hl);
+    if (rp != SMOE_OK) return rp;
+    if (!v->sample_grad || !v->sample_grad_layout) return fail(SMOE_ERR_UNSUPPORTED, fn + ": no kernel variant for this handle");
+    smoe::SampleGradArgs a;
+    std::memset(&a, 0, sizeof a);
+    const float* const no_axes[3] = {nullptr, nullptr, nullptr};
+    const int32_t whole[3] = {1, 1, 1};
+    int64_t ext[3] = {1, 1, 1};
+    for (int l = 0; l < D; ++l) ext[l] = length[l];
+    a.s.r = render_args(h, 0, (int32_t)total, *p, active, h->mus_grid, no_axes, whole, grid, ext, nullptr, SMOE_IMAGE_F32, nullptr);
+    a.s.points = points; a.s.num_points = num_points; a.s.block = block;
+    a.s.vec_blk = ((uintptr_t)block % 16 == 0) ? 1 : 0;
+    a.jac = jac; a.values = values;
+    a.vec_jac = ((uintptr_t)jac % 16 == 0) ? 1 : 0;
+    a.vec_val = ((uintptr_t)values % 16 == 0) ? 1 : 0;
+    for (int l = 0; l < SMOE_MAX_DIM; ++l) { a.s.n[l] = 1; a.s.length[l] = 1.0f; }
+    for (int l = 0; l < D; ++l) {
+        const int n = h->cfg.block_shape[l];
+        a.s.n[l] = n;
+        a.s.length[l] = (float)length[l];
+        a.du_dx[l] = (n > 1) ? (float)(1.0 / (n - 1)) : 0.0f;
+        if (!any || n < 2 || !(blend[l] > 0.0f)) continue;
+        a.s.s0[l] = (float)(-0.5 / (n - 1));
+        a.s.s1[l] = (float)(1.0 + 0.5 / (n - 1));
+        a.s.band[l] = (float)((double)blend[l] / (n - 1));
+        a.s.pitch[l] = (float)((double)n / (n - 1));
+    }
+    // SMOE_SAMPLE_RECORDS (tuning / test hook): as in smoe_sample
+    long long records = -1;
+    if (const char* e = std::getenv("SMOE_SAMPLE_RECORDS")) {
+        char* end = nullptr;
+        const long long r = std::strtoll(e, &end, 10);
+        if (end != e && r >= 0) records = r;
+    }
+    smoe::RenderLayout lay;
+    const char* const unsupported = "the launch would need 2^31 or more workgroups or more than 160 KB of LDS (or the graph variant is not built for the triple)";
+    const int rc = decoder_launched(fn, v->sample_grad_layout(a, records, lay), unsupported);
+    if (rc != SMOE_OK) return rc;
+#if !SMOE_HOST_TEST
+    return decoder_launched(fn, v->sample_grad(a, lay, (hipStream_t)stream), unsupported);
+#else
+    (void)stream;
+    return SMOE_OK;
+#endif
+}
+
 int smoe_update_kernel_list(smoe_handle h, int32_t num_blocks, const smoe_params* p,
                             uint32_t* active, void* stream) {
     if (!h) return fail(SMOE_ERR_INVALID, "smoe_update_kernel_list: null handle");

@@ -204,6 +204,16 @@ struct SampleArgs {
     int rec_cap;              // a workgroup stages the records of its box when the box has at most this many blocks
 };
 
+// smoe_sample_grad (smoe_sample_grad.hip.h): the model's spatial derivative at a list of arbitrary positions.  s: the points, the
+// blocks and the blend as for smoe_sample (s.r.image / s.r.argmax are not used); s.block: [N] or null.
+struct SampleGradArgs {
+    SampleArgs s;
+    float* jac;               // [N, D, C] dV_c / dx_l per source pixel
+    float* values;            // [N, C] the value before the lattice, or null
+    int vec_jac, vec_val;     // the plane's base is 16-byte aligned: vector stores
+    float du_dx[SMOE_MAX_DIM];       // block units per source pixel, 1 / (n - 1); 0 on an axis of one pixel per block
+};
+
 // What the launcher of a block decoder derives from checked arguments, next to the geometry fields of RenderArgs (and off_w
 // of RenderBlendArgs) it fills: a pure host computation (render_layout / render_blend_layout), also run without a device
 struct RenderLayout {
@@ -254,6 +264,9 @@ struct Variant {
     // < 0 none), and the launch of a planned call
     hipError_t (*sample_layout)(SampleArgs&, int hl, long long records, RenderLayout&);
     hipError_t (*sample)(const SampleArgs&, const RenderLayout&, hipStream_t);
+    // point derivative (smoe_sample_grad.hip.h), same conventions
+    hipError_t (*sample_grad_layout)(SampleGradArgs&, long long records, RenderLayout&);
+    hipError_t (*sample_grad)(const SampleGradArgs&, const RenderLayout&, hipStream_t);
 };
 
 // ---- shared-kernel image mode (smoe_shared.hip) ----------------------------------------------

@@ -476,6 +476,58 @@ class BlockEngine(_Engine):
         res = (out,) + ((am,) if want_argmax else ()) + ((bk,) if want_block else ())
         return res if len(res) > 1 else out
 
+    def sample_grad(self, params, active, grid, length, points, blend=None, out=None, want_values=False, want_block=False,
+                    center_grid=None):
+        """Point derivative (include/smoe_hip.h: smoe_sample_grad): the exact spatial derivative of the model at the positions
+        ``points`` -- ``sample``'s points, blocks, lists, ``center_grid`` and ``blend`` -- into ``[N, d, C]`` float32:
+        ``jac[i, l, c] = dV_c / dx_l`` per source pixel, of the value before the lattice.  Points outside the image give 0.
+        Returns the Jacobian, then with ``want_values`` the float32 values before the lattice ``[N, C]`` and with
+        ``want_block`` the int32 image-wide block indices ``[N]`` (-1: outside)."""
+        d = self.cfg.dim
+        who = "sample_grad"
+        grid = [int(g) for g in grid]
+        length = [int(v) for v in length]
+        if len(grid) != d or len(length) != d:
+            raise ValueError(f"{who}: grid and length need {d} entries")
+        total = 1
+        for g in grid:
+            total *= g
+        self._check_params(params, total)
+        if active is not None and (tuple(active.shape) != (total,) or active.dtype != torch.int32 or active.device != self.device):
+            raise ValueError(f"{who}: active must be int32 [{total}] on {self.device}")
+        if points.dim() != 2 or points.shape[1] != d or points.dtype != torch.float32 or not points.is_contiguous() \
+                or points.device != self.device:
+            raise ValueError(f"{who}: points must be a contiguous float32 tensor [N, {d}] on {self.device}")
+        N = int(points.shape[0])
+        bl = None
+        if blend is not None:
+            bl = [float(v) for v in np.atleast_1d(blend)]
+            bl = bl * d if len(bl) == 1 else bl
+            if len(bl) != d:
+                raise ValueError(f"{who}: blend needs one value or {d}")
+        shape = (N, d, self.cfg.channels)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"{who}: out must be a contiguous float32 tensor {shape} on {self.device}")
+        val = torch.empty((N, self.cfg.channels), dtype=torch.float32, device=self.device) if want_values else None
+        bk = torch.empty((N,), dtype=torch.int32, device=self.device) if want_block else None
+        cp = self._cparams(params)
+        held = getattr(self, "_center_grid", None)
+        if center_grid is not None:                          # the image-wide centre grid around the launch alone
+            self.set_center_grid(center_grid)
+        try:
+            rc = self.lib.smoe_sample_grad(self._h, C.byref(cp), _ptr(active), _slots(C.c_int32, grid, 1),
+                                           _slots(C.c_int32, length, 1), _ptr(points), N,
+                                           None if bl is None else _slots(C.c_float, bl, 0.0), _ptr(out), _ptr(val), _ptr(bk),
+                                           self._stream())
+        finally:
+            if center_grid is not None:
+                self.set_center_grid(held)
+        _lib.check(rc)
+        res = (out,) + ((val,) if want_values else ()) + ((bk,) if want_block else ())
+        return res if len(res) > 1 else out
+
     def fit(self, target, params, state: AdamState, active, n_iters: int, loss_w=None, diverged=None,
             loss0=None, loss_out=None, sse_out=None, loss_w_is_sample=False):
         """loss_w_is_sample: ``loss_w`` is a pixel sub-sample (N / n for the drawn pixels, 0 otherwise; smoe.py:1664-1667):

@@ -942,6 +942,63 @@ class Smoe(_SmoeBase):
         ``options`` are ``sample``'s."""
         return self.sample(blk.warp_points(matrix, size), **options)
 
+    def sample_grad(self, points, quantized=False, want_values=False, to_host=True, blend=0.0):
+        """The model's exact spatial derivative at arbitrary positions, on the device (the engine's ``sample_grad``;
+        include/smoe_hip.h: smoe_sample_grad): an edge map, a structure tensor, the temporal slope of a video model, a
+        sub-pixel refinement or alignment step.  Differences of ``sample()`` sit on the 8-bit lattice; this is the closed-form
+        derivative of the value before the lattice, with the gate mask and the clip held piecewise constant.  ``points``,
+        ``quantized``, ``blend`` and the kernel lists are ``sample``'s.  Returns ``[..., d, C]`` float32,
+        ``jac[..., l, c] = dV_c / dx_l`` per source pixel (0 outside the image); with ``want_values`` also the float32
+        values before the lattice ``[..., C]``.  ``to_host=False`` returns device tensors.  Several ranks: as ``sample``."""
+        d, n = self.dim_domain, self.batch_size_valued
+        bl = [float(v) for v in np.atleast_1d(blend)]
+        bl = bl * d if len(bl) == 1 else bl
+        if len(bl) != d:
+            raise ValueError(f"sample_grad: blend needs one value or {d}")
+        for v, nl in zip(bl, n):
+            if not np.isfinite(v) or v < 0 or v > nl / 2:
+                raise ValueError("sample_grad: blend must lie within 0 .. block size / 2 on every axis")
+        eng = self._engine
+        if not hasattr(eng, "sample_grad"):
+            raise NotImplementedError("this engine has no sample_grad()")
+        dev = eng.device
+        pts = points if torch.is_tensor(points) else torch.from_numpy(np.ascontiguousarray(np.asarray(points), dtype=np.float32))
+        if pts.dim() < 1 or pts.shape[-1] != d:
+            raise ValueError(f"sample_grad: points need a trailing axis of {d} coordinates")
+        lead = tuple(pts.shape[:-1])
+        pts = pts.to(device=dev, dtype=torch.float32).reshape(-1, d).contiguous()
+        params, active, center = self._whole_model(quantized)
+        res = eng.sample_grad(params, active, self.grid, [int(v) for v in self.image.shape[:d]], pts,
+                              blend=bl if any(v > 0 for v in bl) else None, want_values=want_values, center_grid=center)
+        jac, val = res if want_values else (res, None)
+        jac = jac.reshape(lead + (d, self.channels))
+        if val is not None:
+            val = val.reshape(lead + (self.channels,))
+        if to_host:
+            jac = jac.cpu().numpy()
+            val = None if val is None else val.cpu().numpy()
+        return (jac, val) if want_values else jac
+
+    def render_warp_grad(self, matrix, size, wrt="source", **options):
+        """The derivative of an affine view: ``sample_grad`` at the cell centres of ``blocks.warp_points(matrix, size)``,
+        ``[*size, d, C]``.  ``wrt="source"``: per source pixel, as ``sample_grad`` gives it; ``wrt="view"``: per output cell,
+        the chain rule through ``x = M (i + 0.5) + t`` applied on the device, ``J_view[..., m, c] = sum_l J[..., l, c] M[l, m]``.
+        ``options`` are ``sample_grad``'s."""
+        if wrt not in ("source", "view"):
+            raise ValueError('render_warp_grad: wrt must be "source" or "view"')
+        to_host = options.pop("to_host", True)
+        want_values = options.get("want_values", False)
+        res = self.sample_grad(blk.warp_points(matrix, size), to_host=False, **options)
+        jac, val = res if want_values else (res, None)
+        if wrt == "view":
+            d = self.dim_domain
+            M = torch.from_numpy(np.ascontiguousarray(np.asarray(matrix, dtype=np.float64)[:, :d], dtype=np.float32)).to(jac.device)
+            jac = torch.einsum("...lc,lm->...mc", jac, M).contiguous()
+        if to_host:
+            jac = jac.cpu().numpy()
+            val = None if val is None else val.cpu().numpy()
+        return (jac, val) if want_values else jac
+
     # hooks of _render
     def _engine_render_blend(self, params, active, axes, grid, extent, out, tdt, want_argmax, blend):
         # the engine reads the neighbours of this rank's blocks: with several ranks, everyone's parameters and list words
