@@ -880,6 +880,81 @@ int render_launch(smoe_handle h, const char* fn, const smoe::RenderArgs& a, void
 #endif
 }
 
+// blend (null: none): every axis finite and within 0 .. block_shape / 2.  *any: some axis has a band to blend in.
+int blend_check(smoe_handle h, const std::string& fn, const float blend[3], bool* any) {
+    *any = false;
+    if (!blend) return SMOE_OK;
+    for (int l = 0; l < h->cfg.dim; ++l) {
+        const int n = h->cfg.block_shape[l];
+        if (!std::isfinite(blend[l]) || blend[l] < 0.0f || blend[l] > 0.5f * (float)n)
+            return fail(SMOE_ERR_INVALID, fn + ": blend[" + std::to_string(l) + "] must be finite and within 0 .. block_shape / 2");
+        *any = *any || (blend[l] > 0.0f && n > 1);
+    }
+    return SMOE_OK;
+}
+
+// the cross-fade window of an axis of n >= 2 pixels per block and a band of `blend` source pixels, in block units
+void blend_window(int n, float blend, float& s0, float& s1, float& band, float& pitch) {
+    s0 = (float)(-0.5 / (n - 1));
+    s1 = (float)(1.0 + 0.5 / (n - 1));
+    band = (float)((double)blend / (n - 1));
+    pitch = (float)((double)n / (n - 1));
+}
+
+// The block grid and the image extent of a point decoder.  *total: prod(grid); *exact: grid * block_shape <= 2^24 on every axis.
+int point_grid_check(smoe_handle h, const std::string& fn, const int32_t grid[3], const int32_t length[3], long long* total,
+                     bool* exact) {
+    *total = 1;
+    *exact = true;
+    for (int l = 0; l < h->cfg.dim; ++l) {
+        const std::string ax = "[" + std::to_string(l) + "]";
+        const long long n = h->cfg.block_shape[l];
+        if (grid[l] < 1) return fail(SMOE_ERR_INVALID, fn + ": grid" + ax + " must be >= 1");
+        *total *= grid[l];
+        if (*total > 0x7fffffffLL) return fail(SMOE_ERR_INVALID, fn + ": grid has more than 2^31 blocks");
+        if (length[l] < 1 || length[l] > grid[l] * n)
+            return fail(SMOE_ERR_INVALID, fn + ": length" + ax + " must be 1 .. grid * block_shape");
+        *exact = *exact && grid[l] * n <= (1LL << 24);
+    }
+    return SMOE_OK;
+}
+
+// The checked arguments of a point decoder as the kernels take them: the whole image's blocks, no axis tables, the points,
+// the windows of the axes that blend (any: blend_check's).
+smoe::SampleArgs sample_args(smoe_handle h, long long total, const smoe_params& p, const uint32_t* active, const int32_t grid[3],
+                             const int32_t length[3], const float* points, int64_t num_points, const float blend[3], bool any,
+                             void* values, int32_t image_format, uint8_t* argmax, int32_t* block) {
+    const int D = h->cfg.dim;
+    smoe::SampleArgs a;
+    std::memset(&a, 0, sizeof a);
+    const float* const no_axes[3] = {nullptr, nullptr, nullptr};
+    const int32_t whole[3] = {1, 1, 1};
+    int64_t ext[3] = {1, 1, 1};
+    for (int l = 0; l < D; ++l) ext[l] = length[l];
+    a.r = render_args(h, 0, (int32_t)total, p, active, h->mus_grid, no_axes, whole, grid, ext, values, image_format, argmax);
+    a.points = points; a.num_points = num_points; a.block = block;
+    a.vec_blk = ((uintptr_t)block % 16 == 0) ? 1 : 0;
+    for (int l = 0; l < SMOE_MAX_DIM; ++l) { a.n[l] = 1; a.length[l] = 1.0f; }
+    for (int l = 0; l < D; ++l) {
+        const int n = h->cfg.block_shape[l];
+        a.n[l] = n;
+        a.length[l] = (float)length[l];
+        if (any && n >= 2 && blend[l] > 0.0f) blend_window(n, blend[l], a.s0[l], a.s1[l], a.band[l], a.pitch[l]);
+    }
+    return a;
+}
+
+// SMOE_SAMPLE_RECORDS (tuning / test hook): cap on the records a workgroup of a point decoder stages; 0: always the direct
+// path; unset or not a number >= 0: -1, no cap
+long long sample_records() {
+    if (const char* e = std::getenv("SMOE_SAMPLE_RECORDS")) {
+        char* end = nullptr;
+        const long long r = std::strtoll(e, &end, 10);
+        if (end != e && r >= 0) return r;
+    }
+    return -1;
+}
+
 }  // namespace
 
 int smoe_render(smoe_handle h, int32_t first_block, int32_t num_blocks, const smoe_params* p, const uint32_t* active,
@@ -902,12 +977,8 @@ int smoe_render_blend(smoe_handle h, int32_t first_block, int32_t num_blocks, co
     if (!blend) return fail(SMOE_ERR_INVALID, std::string(fn) + ": blend is required");
     const int D = h->cfg.dim, K = h->cfg.kernels, Cn = h->cfg.channels;
     bool any = false;
-    for (int l = 0; l < D; ++l) {
-        const int n = h->cfg.block_shape[l];
-        if (!std::isfinite(blend[l]) || blend[l] < 0.0f || blend[l] > 0.5f * (float)n)
-            return fail(SMOE_ERR_INVALID, std::string(fn) + ": blend[" + std::to_string(l) + "] must be finite and within 0 .. block_shape / 2");
-        any = any || (blend[l] > 0.0f && n > 1);
-    }
+    const int rb = blend_check(h, fn, blend, &any);
+    if (rb != SMOE_OK) return rb;
     if (num_blocks == 0) return SMOE_OK;
     if (!any) {
         // nothing to blend: smoe_render's kernel on the shard's slice of the image-wide arrays
@@ -928,11 +999,7 @@ int smoe_render_blend(smoe_handle h, int32_t first_block, int32_t num_blocks, co
     b.r = render_args(h, first_block, num_blocks, *p, active, h->mus_grid, axis_coords, samples, grid, extent, image, image_format, argmax);
     for (int l = 0; l < D; ++l) {
         const int n = h->cfg.block_shape[l];
-        if (n < 2) continue;                               // one pixel per block on this axis: no pitch, nothing to blend
-        b.s0[l] = (float)(-0.5 / (n - 1));
-        b.s1[l] = (float)(1.0 + 0.5 / (n - 1));
-        b.band[l] = (float)((double)blend[l] / (n - 1));
-        b.pitch[l] = (float)((double)n / (n - 1));
+        if (n >= 2) blend_window(n, blend[l], b.s0[l], b.s1[l], b.band[l], b.pitch[l]);   // (one pixel per block: no pitch, nothing to blend)
     }
 #if !SMOE_HOST_TEST
     return decoder_launched(fn, v->render_blend(b, hl, v->G, (hipStream_t)stream), kRenderUnsupported);
@@ -980,14 +1047,8 @@ int smoe_render_view(smoe_handle h, const smoe_params* p, const uint32_t* active
         ext[l] = st[view_blocks[l]];
     }
     bool any = false;
-    if (blend) {
-        for (int l = 0; l < D; ++l) {
-            const int n = h->cfg.block_shape[l];
-            if (!std::isfinite(blend[l]) || blend[l] < 0.0f || blend[l] > 0.5f * (float)n)
-                return fail(SMOE_ERR_INVALID, fn + ": blend[" + std::to_string(l) + "] must be finite and within 0 .. block_shape / 2");
-            any = any || (blend[l] > 0.0f && n > 1);
-        }
-    }
+    const int rb = blend_check(h, fn, blend, &any);
+    if (rb != SMOE_OK) return rb;
     if (image_format == SMOE_IMAGE_U8 && h->cfg.precision > 8)
         return fail(SMOE_ERR_UNSUPPORTED, fn + ": SMOE_IMAGE_U8 needs precision <= 8");
 
@@ -1006,11 +1067,7 @@ int smoe_render_view(smoe_handle h, const smoe_params* p, const uint32_t* active
     for (int l = 0; l < D; ++l) {
         hst.start[l] = axis_start[l]; hst.first[l] = view_first[l]; hst.blocks[l] = view_blocks[l];
         const int n = h->cfg.block_shape[l];
-        if (!any || n < 2 || !(blend[l] > 0.0f)) continue;
-        a.s0[l] = (float)(-0.5 / (n - 1));
-        a.s1[l] = (float)(1.0 + 0.5 / (n - 1));
-        a.band[l] = (float)((double)blend[l] / (n - 1));
-        a.pitch[l] = (float)((double)n / (n - 1));
+        if (any && n >= 2 && blend[l] > 0.0f) blend_window(n, blend[l], a.s0[l], a.s1[l], a.band[l], a.pitch[l]);
     }
     smoe::ViewPlan plan;
     smoe::RenderLayout lay;
@@ -1050,28 +1107,11 @@ int smoe_sample(smoe_handle h, const smoe_params* p, const uint32_t* active, con
     if (image_format != SMOE_IMAGE_F32 && image_format != SMOE_IMAGE_U8)
         return fail(SMOE_ERR_INVALID, fn + ": image_format must be SMOE_IMAGE_F32 or SMOE_IMAGE_U8");
     if (num_points < 0) return fail(SMOE_ERR_INVALID, fn + ": num_points must be >= 0");
-    const int D = h->cfg.dim;
     long long total = 1;
-    bool exact = true;
-    for (int l = 0; l < D; ++l) {
-        const std::string ax = "[" + std::to_string(l) + "]";
-        const long long n = h->cfg.block_shape[l];
-        if (grid[l] < 1) return fail(SMOE_ERR_INVALID, fn + ": grid" + ax + " must be >= 1");
-        total *= grid[l];
-        if (total > 0x7fffffffLL) return fail(SMOE_ERR_INVALID, fn + ": grid has more than 2^31 blocks");
-        if (length[l] < 1 || length[l] > grid[l] * n)
-            return fail(SMOE_ERR_INVALID, fn + ": length" + ax + " must be 1 .. grid * block_shape");
-        exact = exact && grid[l] * n <= (1LL << 24);
-    }
-    bool any = false;
-    if (blend) {
-        for (int l = 0; l < D; ++l) {
-            const int n = h->cfg.block_shape[l];
-            if (!std::isfinite(blend[l]) || blend[l] < 0.0f || blend[l] > 0.5f * (float)n)
-                return fail(SMOE_ERR_INVALID, fn + ": blend[" + std::to_string(l) + "] must be finite and within 0 .. block_shape / 2");
-            any = any || (blend[l] > 0.0f && n > 1);
-        }
-    }
+    bool exact = true, any = false;
+    int rc = point_grid_check(h, fn, grid, length, &total, &exact);
+    if (rc == SMOE_OK) rc = blend_check(h, fn, blend, &any);
+    if (rc != SMOE_OK) return rc;
     if (num_points == 0) return SMOE_OK;
     if (!points) return fail(SMOE_ERR_INVALID, fn + ": points is required");
     if (!values) return fail(SMOE_ERR_INVALID, fn + ": values is required");
@@ -1085,36 +1125,11 @@ int smoe_sample(smoe_handle h, const smoe_params* p, const uint32_t* active, con
     const int rp = render_plan(h, fn.c_str(), (int32_t)total, &v, &hl);
     if (rp != SMOE_OK) return rp;
     if (!v->sample || !v->sample_layout) return fail(SMOE_ERR_UNSUPPORTED, fn + ": no kernel variant for this handle");
-    smoe::SampleArgs a;
-    std::memset(&a, 0, sizeof a);
-    const float* const no_axes[3] = {nullptr, nullptr, nullptr};
-    const int32_t whole[3] = {1, 1, 1};
-    int64_t ext[3] = {1, 1, 1};
-    for (int l = 0; l < D; ++l) ext[l] = length[l];
-    a.r = render_args(h, 0, (int32_t)total, *p, active, h->mus_grid, no_axes, whole, grid, ext, values, image_format, argmax);
-    a.points = points; a.num_points = num_points; a.block = block;
-    a.vec_blk = ((uintptr_t)block % 16 == 0) ? 1 : 0;
-    for (int l = 0; l < SMOE_MAX_DIM; ++l) { a.n[l] = 1; a.length[l] = 1.0f; }
-    for (int l = 0; l < D; ++l) {
-        const int n = h->cfg.block_shape[l];
-        a.n[l] = n;
-        a.length[l] = (float)length[l];
-        if (!any || n < 2 || !(blend[l] > 0.0f)) continue;
-        a.s0[l] = (float)(-0.5 / (n - 1));
-        a.s1[l] = (float)(1.0 + 0.5 / (n - 1));
-        a.band[l] = (float)((double)blend[l] / (n - 1));
-        a.pitch[l] = (float)((double)n / (n - 1));
-    }
-    // SMOE_SAMPLE_RECORDS (tuning / test hook): cap on the records a workgroup stages; 0: always the direct path
-    long long records = -1;
-    if (const char* e = std::getenv("SMOE_SAMPLE_RECORDS")) {
-        char* end = nullptr;
-        const long long r = std::strtoll(e, &end, 10);
-        if (end != e && r >= 0) records = r;
-    }
+    smoe::SampleArgs a = sample_args(h, total, *p, active, grid, length, points, num_points, blend, any, values, image_format,
+                                     argmax, block);
     smoe::RenderLayout lay;
     const char* const unsupported = "the launch would need 2^31 or more workgroups (or the graph variant is not built for the triple)";
-    const int rc = decoder_launched(fn, v->sample_layout(a, hl, records, lay), unsupported);
+    rc = decoder_launched(fn, v->sample_layout(a, hl, sample_records(), lay), unsupported);
     if (rc != SMOE_OK) return rc;
 #if !SMOE_HOST_TEST
     return decoder_launched(fn, v->sample(a, lay, (hipStream_t)stream), unsupported);
@@ -1133,28 +1148,11 @@ int smoe_sample_grad(smoe_handle h, const smoe_params* p, const uint32_t* active
     if (!grid) return fail(SMOE_ERR_INVALID, fn + ": grid is required");
     if (!length) return fail(SMOE_ERR_INVALID, fn + ": length is required");
     if (num_points < 0) return fail(SMOE_ERR_INVALID, fn + ": num_points must be >= 0");
-    const int D = h->cfg.dim;
     long long total = 1;
-    bool exact = true;
-    for (int l = 0; l < D; ++l) {
-        const std::string ax = "[" + std::to_string(l) + "]";
-        const long long n = h->cfg.block_shape[l];
-        if (grid[l] < 1) return fail(SMOE_ERR_INVALID, fn + ": grid" + ax + " must be >= 1");
-        total *= grid[l];
-        if (total > 0x7fffffffLL) return fail(SMOE_ERR_INVALID, fn + ": grid has more than 2^31 blocks");
-        if (length[l] < 1 || length[l] > grid[l] * n)
-            return fail(SMOE_ERR_INVALID, fn + ": length" + ax + " must be 1 .. grid * block_shape");
-        exact = exact && grid[l] * n <= (1LL << 24);
-    }
-    bool any = false;
-    if (blend) {
-        for (int l = 0; l < D; ++l) {
-            const int n = h->cfg.block_shape[l];
-            if (!std::isfinite(blend[l]) || blend[l] < 0.0f || blend[l] > 0.5f * (float)n)
-                return fail(SMOE_ERR_INVALID, fn + ": blend[" + std::to_string(l) + "] must be finite and within 0 .. block_shape / 2");
-            any = any || (blend[l] > 0.0f && n > 1);
-        }
-    }
+    bool exact = true, any = false;
+    int rc = point_grid_check(h, fn, grid, length, &total, &exact);
+    if (rc == SMOE_OK) rc = blend_check(h, fn, blend, &any);
+    if (rc != SMOE_OK) return rc;
     if (num_points == 0) return SMOE_OK;
     if (!points) return fail(SMOE_ERR_INVALID, fn + ": points is required");
     if (!jac) return fail(SMOE_ERR_INVALID, fn + ": jac is required");
@@ -1168,38 +1166,17 @@ int smoe_sample_grad(smoe_handle h, const smoe_params* p, const uint32_t* active
     if (!v->sample_grad || !v->sample_grad_layout) return fail(SMOE_ERR_UNSUPPORTED, fn + ": no kernel variant for this handle");
     smoe::SampleGradArgs a;
     std::memset(&a, 0, sizeof a);
-    const float* const no_axes[3] = {nullptr, nullptr, nullptr};
-    const int32_t whole[3] = {1, 1, 1};
-    int64_t ext[3] = {1, 1, 1};
-    for (int l = 0; l < D; ++l) ext[l] = length[l];
-    a.s.r = render_args(h, 0, (int32_t)total, *p, active, h->mus_grid, no_axes, whole, grid, ext, nullptr, SMOE_IMAGE_F32, nullptr);
-    a.s.points = points; a.s.num_points = num_points; a.s.block = block;
-    a.s.vec_blk = ((uintptr_t)block % 16 == 0) ? 1 : 0;
+    a.s = sample_args(h, total, *p, active, grid, length, points, num_points, blend, any, nullptr, SMOE_IMAGE_F32, nullptr, block);
     a.jac = jac; a.values = values;
     a.vec_jac = ((uintptr_t)jac % 16 == 0) ? 1 : 0;
     a.vec_val = ((uintptr_t)values % 16 == 0) ? 1 : 0;
-    for (int l = 0; l < SMOE_MAX_DIM; ++l) { a.s.n[l] = 1; a.s.length[l] = 1.0f; }
-    for (int l = 0; l < D; ++l) {
+    for (int l = 0; l < h->cfg.dim; ++l) {
         const int n = h->cfg.block_shape[l];
-        a.s.n[l] = n;
-        a.s.length[l] = (float)length[l];
         a.du_dx[l] = (n > 1) ? (float)(1.0 / (n - 1)) : 0.0f;
-        if (!any || n < 2 || !(blend[l] > 0.0f)) continue;
-        a.s.s0[l] = (float)(-0.5 / (n - 1));
-        a.s.s1[l] = (float)(1.0 + 0.5 / (n - 1));
-        a.s.band[l] = (float)((double)blend[l] / (n - 1));
-        a.s.pitch[l] = (float)((double)n / (n - 1));
-    }
-    // SMOE_SAMPLE_RECORDS (tuning / test hook): as in smoe_sample
-    long long records = -1;
-    if (const char* e = std::getenv("SMOE_SAMPLE_RECORDS")) {
-        char* end = nullptr;
-        const long long r = std::strtoll(e, &end, 10);
-        if (end != e && r >= 0) records = r;
     }
     smoe::RenderLayout lay;
     const char* const unsupported = "the launch would need 2^31 or more workgroups or more than 160 KB of LDS (or the graph variant is not built for the triple)";
-    const int rc = decoder_launched(fn, v->sample_grad_layout(a, records, lay), unsupported);
+    rc = decoder_launched(fn, v->sample_grad_layout(a, sample_records(), lay), unsupported);
     if (rc != SMOE_OK) return rc;
 #if !SMOE_HOST_TEST
     return decoder_launched(fn, v->sample_grad(a, lay, (hipStream_t)stream), unsupported);

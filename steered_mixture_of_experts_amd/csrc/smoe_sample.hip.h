@@ -11,21 +11,24 @@
 // cross-faded with the neighbouring blocks exactly as render_blend_kernel / render_view_kernel do it.  argmax is the own
 // block's.  Nothing a point computes depends on the other points, on its place in the list or on how the launch is cut.
 //
-// Arrangement.  A workgroup of 256 lanes takes SAMPLE_PPL * 256 consecutive points: lane t takes the SAMPLE_PPL points from
-// t * SAMPLE_PPL on, so a lane's points and those of its neighbours are neighbours in the list, a row-major warp keeps a
-// wavefront inside one or two blocks and a lane mostly inside one.  The workgroup first resolves its points and takes the
-// per-axis minimum and maximum of their block indices (with BLEND widened by one inside the grid).
+// Arrangement: that of the point frame (point_box ... point_store_plane below), of which smoe_sample_grad.hip.h is built;
+// this kernel spells most of it out in its own text (see the frame's comment for why).  A workgroup of 256 lanes takes
+// PPL * 256 consecutive points (PPL = SAMPLE_PPL here): lane t takes the PPL points from t * PPL on, so a lane's points and
+// those of its neighbours are neighbours in the list, a row-major warp keeps a wavefront inside one or two blocks and a lane
+// mostly inside one.  The workgroup first resolves its points and takes the per-axis minimum and maximum of their block
+// indices (with BLEND widened by one inside the grid).
 //  * Staged path: the box has no more blocks than the record budget (s.rec_cap).  One lane per block of the box derives its
 //    record (sample_derive: what every lane of render_kernel does for its block) and keeps it in LDS (store_record); a lane
 //    reads a record (load_record) when its point's block differs from the one it holds, and a neighbour's when it needs one.
 //  * Direct path: otherwise.  Every lane derives the record of its point's block -- and of a neighbour it needs -- from global
 //    memory in registers, again with sample_derive, when the block differs from the one it holds.
-// Both paths run the same device functions on the same inputs, so they give the same bits.  The hoisted terms are re-made for
-// every point from its own trailing coordinates (hoist_const): the same fused multiply-adds in the same order as in
-// render_kernel, where those coordinates are lane constants.
-// The workgroup's values, kernel ids and block indices are turned through LDS and leave, after one barrier, as 16-byte
-// non-temporal stores where the plane's base is 16-byte aligned, element-wise at the ragged head and tail
-// (render_store_run): the output is dense, so a workgroup's points are one run per plane.
+// Both paths run the same device functions on the same inputs, so they give the same bits.  A point is located (block,
+// coordinates, record), with BLEND the neighbour window of every axis and the geometry of every corner of the cross-fade
+// are formed, and the planes are stored: the workgroup's results are turned through LDS and leave, after one barrier, as 16-byte non-temporal stores
+// where the plane's base is 16-byte aligned, element-wise at the ragged head and tail (render_store_run) -- the output is
+// dense, so a workgroup's points are one run per plane.  What a point computes is the kernel's: here the hoisted terms are
+// re-made for every point from its own trailing coordinates (hoist_const), the same fused multiply-adds in the same order as
+// in render_kernel, where those coordinates are lane constants.
 #ifndef SMOE_SAMPLE_HIP_H
 #define SMOE_SAMPLE_HIP_H
 
@@ -78,10 +81,143 @@ __device__ __forceinline__ void sample_derive(const RenderArgs& a, long long id,
     B.template derive<IC>(a.kc);
 }
 
+// The point decoders' frame: what a point decoder does around the evaluation of a point, and nothing of the evaluation.  A
+// workgroup of 256 lanes takes PPL * 256 consecutive points [p0, pe), lane t the PPL points from t * PPL on.  LDS: box (per
+// axis minimum, maximum of the block indices) | derived records (s_rec, from r.off_par) | the kernel's own staging (from
+// r.off_stage).  The pieces are free functions over the kernel's own locals p0, pe, lo, nbx, staged and s_rec.
+// sample_grad_kernel is built from all of them; the two lines that give p0 / pe and the staging loop between point_box and
+// the prologue's last barrier stand in its text, word for word as in sample_kernel.
+// sample_kernel (below) uses point_window and point_fetch and keeps the rest in its own text: with these two its
+// instruction stream is the one it had before the frame in every instantiation (in a quarter of them up to four integer
+// additions have their operands swapped).  Any of point_box, point_locate, point_corner or point_store_plane in place of
+// its own lines leaves the compiler the same instructions in another order after inlining, and with that another register
+// allocation and schedule: of the arrangements tried, each either cost some instantiations a wave per SIMD or 0.5 ... 1.4 %
+// of the kernel's time (profiles/render/point_frame_ab.txt).
+
+// The prologue up to the box, with two barriers: every lane of the workgroup runs it, once, before anything else.  The
+// workgroup resolves its points and takes the box of their blocks: first block lo and blocks nbx per axis, with BLEND widened
+// by one inside the grid.  Returns the blocks of the box; where they are no more than the record budget (s.rec_cap) the
+// kernel has one lane per block derive its record into LDS (staged, workgroup-uniform) and closes with a third barrier.
+template <int D, int PPL, bool BLEND>
+__device__ __forceinline__ long long point_box(const SampleArgs& s, float* lds, long long p0, long long pe, int (&lo)[D],
+                                               int (&nbx)[D]) {
+    const RenderArgs& a = s.r;
+    const int tid = threadIdx.x;
+    int* s_box = reinterpret_cast<int*>(lds);
+    if (tid < D) { s_box[2 * tid] = 0x7fffffff; s_box[2 * tid + 1] = -1; }
+    __syncthreads();
+    for (int j = 0; j < PPL; ++j) {
+        const long long i = p0 + tid * PPL + j;
+        if (i >= pe) break;
+        int g[D];
+        bool in = true;
+#pragma unroll
+        for (int l = 0; l < D; ++l) {
+            float u;
+            in = sample_resolve(s.points[i * D + l], s.n[l], s.length[l], g[l], u) && in;
+        }
+        if (in) {
+#pragma unroll
+            for (int l = 0; l < D; ++l) {                  // (a stale read only costs an atomic that changes nothing)
+                if (g[l] < s_box[2 * l]) atomicMin(&s_box[2 * l], g[l]);
+                if (g[l] > s_box[2 * l + 1]) atomicMax(&s_box[2 * l + 1], g[l]);
+            }
+        }
+    }
+    __syncthreads();
+    long long nrec = 1;
+#pragma unroll
+    for (int l = 0; l < D; ++l) {
+        int b0 = s_box[2 * l], b1 = s_box[2 * l + 1];
+        if (BLEND && s.band[l] > 0.0f) { b0 = max(b0 - 1, 0); b1 = min(b1 + 1, a.grid[l] - 1); }
+        lo[l] = b0;
+        nbx[l] = (b1 >= b0) ? b1 - b0 + 1 : 0;
+        nrec *= nbx[l];
+    }
+    return nrec;
+}
+
+// the record of block (id image-wide, rec in the box) into registers
+template <int D, int C, int K, bool QUANT, bool IC>
+__device__ __forceinline__ void point_fetch(const SampleArgs& s, bool staged, const float* s_rec, BlockRegs<D, C, K>& B,
+                                            long long id, int rec) {
+    if (staged) load_record<D, C, K>(B, s_rec + rec * BlendRec<D, C, K>::STRIDE);
+    else sample_derive<D, C, K, QUANT, IC>(s.r, id, B);
+}
+
+// Point i: false where it is outside (id -1).  Otherwise its block g, its block-unit coordinates x, the block's image-wide
+// index id and its record's index rec in the box.
+template <int D>
+__device__ __forceinline__ bool point_locate(const SampleArgs& s, const int (&lo)[D], const int (&nbx)[D], long long i,
+                                             int (&g)[D], float (&x)[D], long long& id, int& rec) {
+    bool in = true;
+#pragma unroll
+    for (int l = 0; l < D; ++l) in = sample_resolve(s.points[i * D + l], s.n[l], s.length[l], g[l], x[l]) && in;
+    id = -1;
+    rec = 0;
+    if (in) {
+        id = 0;
+#pragma unroll
+        for (int l = 0; l < D; ++l) {
+            id = id * s.r.grid[l] + g[l];
+            rec = rec * nbx[l] + (g[l] - lo[l]);
+        }
+    }
+    return in;
+}
+
+// The neighbour window of axis l at coordinate x in block g: the signed weight w (> 0: towards the high neighbour), the
+// neighbour's side sd and its weight wn = |w|, 0 where the neighbour is outside the grid.
+__device__ __forceinline__ float point_window(const SampleArgs& s, int l, float x, int g, int& sd, float& wn) {
+    float w = 0.0f;
+    if (s.band[l] > 0.0f) {
+        const float whi = fminf(fmaxf(0.5f * (1.0f + (x - s.s1[l]) / s.band[l]), 0.0f), 1.0f);
+        const float wlo = fminf(fmaxf(0.5f * (1.0f + (s.s0[l] - x) / s.band[l]), 0.0f), 1.0f);
+        w = (whi > 0.0f) ? whi : -wlo;
+    }
+    sd = (w > 0.0f) ? 1 : -1;
+    const int gn = g + sd;
+    wn = (gn >= 0 && gn < s.r.grid[l]) ? fabsf(w) : 0.0f;
+    return w;
+}
+
+// Corner cm of a point (bit l = the neighbour on axis l): its weight, the point's coordinates xn in that block, the block's
+// image-wide index nid and its record nrc.  (A neighbour outside the grid has weight 0: nid / nrc are not to be used.)
+template <int D>
+__device__ __forceinline__ float point_corner(const SampleArgs& s, const int (&lo)[D], const int (&nbx)[D], int cm,
+                                              const int (&g)[D], const float (&x)[D], const int (&sd)[D], const float (&wn)[D],
+                                              float (&xn)[D], long long& nid, int& nrc) {
+    float Wc = 1.0f;
+    nid = 0;
+    nrc = 0;
+#pragma unroll
+    for (int l = 0; l < D; ++l) {
+        const bool nb = ((cm >> l) & 1) != 0;
+        const int gg = g[l] + (nb ? sd[l] : 0);
+        Wc *= nb ? wn[l] : 1.0f - wn[l];
+        xn[l] = nb ? x[l] - (float)sd[l] * s.pitch[l] : x[l];
+        nid = nid * s.r.grid[l] + gg;
+        nrc = nrc * nbx[l] + (gg - lo[l]);
+    }
+    return Wc;
+}
+
+// The workgroup's run [p0, pe) of one plane from its staging st (a dword per value, cps values per point) to the dense
+// output: vs = log2 of the values per 16-byte line where the plane's base is 16-byte aligned, else 0; u8: bytes, not dwords.
+template <int PPL>
+__device__ __forceinline__ void point_store_plane(long long p0, long long pe, const uint32_t* st, void* dst, int cps, int vs,
+                                                  bool u8) {
+    const int cpr = ((PPL * RENDER_THREADS * cps + (1 << vs) - 1) >> vs) + 1;      // 16-byte lines the run can touch
+    const long long e0 = p0 * cps, e1 = pe * cps;
+    for (int ch = threadIdx.x; ch < cpr; ch += RENDER_THREADS) {
+        if (u8) render_store_run<true>(st, dst, e0, e1, 0, vs, ch);
+        else render_store_run<false>(st, dst, e0, e1, 0, vs, ch);
+    }
+}
+
 template <int D, int C, int K, int HL, bool QUANT, bool IC, bool BLEND>
 __global__ void __launch_bounds__(RENDER_THREADS) sample_kernel(SampleArgs s) {
     using Lt = Layout<D, C, K>;
-    using Rc = BlendRec<D, C, K>;
     const RenderArgs& a = s.r;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x;
@@ -126,26 +262,26 @@ __global__ void __launch_bounds__(RENDER_THREADS) sample_kernel(SampleArgs s) {
     if (staged) {
         for (int rec = tid; rec < (int)nrec; rec += RENDER_THREADS) {
             long long id = 0;
-            int q = rec, sl[D];
+            int r = rec, sl[D];
 #pragma unroll
             for (int l = D - 1; l >= 0; --l) {
-                const int qq = q / nbx[l];
-                sl[l] = q - qq * nbx[l];
-                q = qq;
+                const int rr = r / nbx[l];
+                sl[l] = r - rr * nbx[l];
+                r = rr;
             }
 #pragma unroll
             for (int l = 0; l < D; ++l) id = id * a.grid[l] + (lo[l] + sl[l]);
             BlockRegs<D, C, K> B;
             sample_derive<D, C, K, QUANT, IC>(a, id, B);
-            store_record<D, C, K>(B, s_rec + rec * Rc::STRIDE);
+            store_record<D, C, K>(B, s_rec + rec * BlendRec<D, C, K>::STRIDE);
         }
     }
     __syncthreads();
 
-    // the record of block (id image-wide, rec in the box) into registers
+    // the record of block (id image-wide, rec in the box) into registers (a lambda, as before the frame: with point_fetch
+    // called directly at its two sites the cross-fade instantiations of triple 3,1,1 lose a wave per SIMD)
     auto fetch = [&](BlockRegs<D, C, K>& B, long long id, int rec) {
-        if (staged) load_record<D, C, K>(B, s_rec + rec * Rc::STRIDE);
-        else sample_derive<D, C, K, QUANT, IC>(a, id, B);
+        point_fetch<D, C, K, QUANT, IC>(s, staged, s_rec, B, id, rec);
     };
 
     BlockRegs<D, C, K> R;
@@ -192,15 +328,7 @@ __global__ void __launch_bounds__(RENDER_THREADS) sample_kernel(SampleArgs s) {
                     bool band = false;
 #pragma unroll
                     for (int l = 0; l < D; ++l) {
-                        float w = 0.0f;
-                        if (s.band[l] > 0.0f) {
-                            const float whi = fminf(fmaxf(0.5f * (1.0f + (x[l] - s.s1[l]) / s.band[l]), 0.0f), 1.0f);
-                            const float wlo = fminf(fmaxf(0.5f * (1.0f + (s.s0[l] - x[l]) / s.band[l]), 0.0f), 1.0f);
-                            w = (whi > 0.0f) ? whi : -wlo;
-                        }
-                        sd[l] = (w > 0.0f) ? 1 : -1;
-                        const int gn = g[l] + sd[l];
-                        wn[l] = (gn >= 0 && gn < a.grid[l]) ? fabsf(w) : 0.0f;
+                        point_window(s, l, x[l], g[l], sd[l], wn[l]);
                         band = band || (wn[l] > 0.0f);
                     }
                     if (band) {
@@ -294,11 +422,12 @@ __global__ void __launch_bounds__(RENDER_THREADS) sample_kernel(SampleArgs s) {
     }
 }
 
-// The launch geometry and the LDS carve-up for checked arguments: pure host code.  records: the cap on the staged records of a
-// workgroup the caller asks for (< 0: none; 0: always the direct path).  The budget: at most SAMPLE_RECORD_BYTES of records
-// -- where not even the smallest set a point needs (its block, with a blend the 3^d around it) fits, nothing is staged --,
-// never more records than the grid has blocks, 160 KB of LDS in all.
-inline hipError_t sample_layout(int D, int C, int rec_floats, long long records, SampleArgs& s, RenderLayout& g) {
+// The launch geometry and the LDS carve-up of a point decoder for checked arguments: pure host code.  stage_dwords: what a
+// point stages, ppl: the points per lane.  records: the cap on the staged records of a workgroup the caller asks for (< 0:
+// none; 0: always the direct path).  The budget: at most SAMPLE_RECORD_BYTES of records -- where not even the smallest set a
+// point needs (its block, with a blend the 3^d around it) fits, nothing is staged --, never more records than the grid has
+// blocks, 160 KB of LDS in all.
+inline hipError_t point_layout(int D, int stage_dwords, int ppl, int rec_floats, long long records, SampleArgs& s, RenderLayout& g) {
     RenderArgs& a = s.r;
     long long cap = (long long)(SAMPLE_RECORD_BYTES / (sizeof(float) * rec_floats));
     long long least = 1, total = 1;
@@ -312,9 +441,9 @@ inline hipError_t sample_layout(int D, int C, int rec_floats, long long records,
     s.rec_cap = (int)cap;
     a.off_par = round_up(2 * D, 4);
     a.off_stage = a.off_par + (int)cap * rec_floats;
-    g.lds_bytes = sizeof(float) * ((size_t)a.off_stage + (size_t)SAMPLE_PPL * RENDER_THREADS * (C + 2));
+    const long long per = (long long)ppl * RENDER_THREADS;
+    g.lds_bytes = sizeof(float) * ((size_t)a.off_stage + (size_t)per * stage_dwords);
     if (g.lds_bytes > 160u * 1024u) return hipErrorNotSupported;
-    const long long per = (long long)SAMPLE_PPL * RENDER_THREADS;
     g.workgroups = (s.num_points + per - 1) / per;
     if (g.workgroups > 0x7fffffffLL) return hipErrorNotSupported;
     return hipSuccess;
@@ -330,7 +459,7 @@ template <int D, int C, int K, bool FULL>
 hipError_t sample_layout(SampleArgs& s, int hl, long long records, RenderLayout& g) {
     if (s.r.kc.qmode != 0 && !FULL) return hipErrorNotSupported;
     g.hl = render_hoisting(D, s.r.kc, hl);
-    return sample_layout(D, C, BlendRec<D, C, K>::STRIDE, records, s, g);
+    return point_layout(D, C + 2, SAMPLE_PPL, BlendRec<D, C, K>::STRIDE, records, s, g);   // a point stages C values, id, block
 }
 
 // The kernel of a planned call (geometry filled by sample_layout): the launch alone.

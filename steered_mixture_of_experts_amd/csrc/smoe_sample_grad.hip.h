@@ -21,12 +21,11 @@
 // Units: jac[i, l, c] = dV_c / du_l / (n_l - 1), per source pixel; 0 on an axis with n_l == 1.  Outside points: jac 0, values
 // 0, block -1.  A point owes nothing to the other points, to its place in the list or to how the launch is cut.
 //
-// Arrangement: sample_kernel's.  256 lanes, SAMPLE_GRAD_PPL consecutive points per lane, the box of the workgroup's block
-// indices, the staged / direct record paths (sample_derive, store_record / load_record; SMOE_SAMPLE_RECORDS caps the staged
-// records): both paths run the same functions on the same inputs and give the same bits.  There is no hoisting level: every
-// point has its own coordinate on every axis, and the forward half of grad_eval is pixel<>'s order of operations without
-// hoisting.  The three planes are turned through LDS and leave as 16-byte non-temporal stores where the plane's base is
-// 16-byte aligned, element-wise at ragged heads and tails (render_store_run, 64-bit element offsets).
+// Arrangement: the point frame of smoe_sample.hip.h (the workgroup's points and box, the staged / direct record
+// paths, locating a point, the neighbour windows and corners, the plane stores) with SAMPLE_GRAD_PPL points per lane; the
+// evaluation, the slopes of the windows and the quotient rule are this kernel's.  There is no hoisting level: every point has
+// its own coordinate on every axis, and the forward half of grad_eval is pixel<>'s order of operations without hoisting.
+// The three planes (Jacobians, values, blocks) are float32 / int32 dwords.
 // Two points per lane, not sample_kernel's four: a point stages D C + C + 1 dwords (13 for d = 3, C = 3), so 512 points
 // take 26 KB beside at most 12 KB of records and four workgroups fit a CU's 160 KB -- the register file, not LDS, sets the
 // occupancy for every triple (DESIGN 3.2g has the figures).  A lane writes its point's D C values at a stride of
@@ -163,49 +162,16 @@ __device__ __forceinline__ void grad_clip(const KernelConsts& kc, const float (&
 
 template <int D, int C, int K, bool QUANT, bool IC, bool BLEND>
 __global__ void __launch_bounds__(RENDER_THREADS) sample_grad_kernel(SampleGradArgs q) {
-    using Rc = BlendRec<D, C, K>;
+    constexpr int per = SAMPLE_GRAD_PPL * RENDER_THREADS;
     const SampleArgs& s = q.s;
     const RenderArgs& a = s.r;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x;
-    constexpr int per = SAMPLE_GRAD_PPL * RENDER_THREADS;
-    const long long p0 = (long long)blockIdx.x * per;       // the workgroup's first point
+    const long long p0 = (long long)blockIdx.x * per;      // the workgroup's points [p0, pe)
     const long long pe = (s.num_points - p0 < per) ? s.num_points : p0 + per;
-
-    // LDS: box (per axis minimum, maximum of the block indices) | derived records | staging (Jacobians, values, block indices)
-    int* s_box = reinterpret_cast<int*>(lds);
-    float* s_rec = lds + a.off_par;
-    if (tid < D) { s_box[2 * tid] = 0x7fffffff; s_box[2 * tid + 1] = -1; }
-    __syncthreads();
-    for (int j = 0; j < SAMPLE_GRAD_PPL; ++j) {
-        const long long i = p0 + tid * SAMPLE_GRAD_PPL + j;
-        if (i >= pe) break;
-        int g[D];
-        bool in = true;
-#pragma unroll
-        for (int l = 0; l < D; ++l) {
-            float u;
-            in = sample_resolve(s.points[i * D + l], s.n[l], s.length[l], g[l], u) && in;
-        }
-        if (in) {
-#pragma unroll
-            for (int l = 0; l < D; ++l) {                  // (a stale read only costs an atomic that changes nothing)
-                if (g[l] < s_box[2 * l]) atomicMin(&s_box[2 * l], g[l]);
-                if (g[l] > s_box[2 * l + 1]) atomicMax(&s_box[2 * l + 1], g[l]);
-            }
-        }
-    }
-    __syncthreads();
     int lo[D], nbx[D];                                     // the box: first block and blocks per axis
-    long long nrec = 1;
-#pragma unroll
-    for (int l = 0; l < D; ++l) {
-        int b0 = s_box[2 * l], b1 = s_box[2 * l + 1];
-        if (BLEND && s.band[l] > 0.0f) { b0 = max(b0 - 1, 0); b1 = min(b1 + 1, a.grid[l] - 1); }
-        lo[l] = b0;
-        nbx[l] = (b1 >= b0) ? b1 - b0 + 1 : 0;
-        nrec *= nbx[l];
-    }
+    float* s_rec = lds + a.off_par;
+    const long long nrec = point_box<D, SAMPLE_GRAD_PPL, BLEND>(s, lds, p0, pe, lo, nbx);
     const bool staged = nrec <= (long long)s.rec_cap;      // workgroup-uniform
     if (staged) {
         for (int rec = tid; rec < (int)nrec; rec += RENDER_THREADS) {
@@ -221,19 +187,14 @@ __global__ void __launch_bounds__(RENDER_THREADS) sample_grad_kernel(SampleGradA
             for (int l = 0; l < D; ++l) id = id * a.grid[l] + (lo[l] + sl[l]);
             BlockRegs<D, C, K> B;
             sample_derive<D, C, K, QUANT, IC>(a, id, B);
-            store_record<D, C, K>(B, s_rec + rec * Rc::STRIDE);
+            store_record<D, C, K>(B, s_rec + rec * BlendRec<D, C, K>::STRIDE);
         }
     }
     __syncthreads();
 
-    // the record of block (id image-wide, rec in the box) into registers
-    auto fetch = [&](BlockRegs<D, C, K>& B, long long id, int rec) {
-        if (staged) load_record<D, C, K>(B, s_rec + rec * Rc::STRIDE);
-        else sample_derive<D, C, K, QUANT, IC>(a, id, B);
-    };
-
     BlockRegs<D, C, K> R;
     long long cur_id = -1;
+    // staging: the Jacobians, the values and the block indices of the workgroup's points
     uint32_t* sj = reinterpret_cast<uint32_t*>(lds + a.off_stage);
     uint32_t* sv = sj + per * (D * C);
     uint32_t* sbk = sv + per * C;
@@ -243,22 +204,12 @@ __global__ void __launch_bounds__(RENDER_THREADS) sample_grad_kernel(SampleGradA
         const long long i = p0 + si;
         if (i < pe) {
             float x[D];
-            int g[D];
-            bool in = true;
-#pragma unroll
-            for (int l = 0; l < D; ++l) in = sample_resolve(s.points[i * D + l], s.n[l], s.length[l], g[l], x[l]) && in;
+            int g[D], rec;
+            long long id;
             float v[C], dv[D][C];
-            long long id = -1;
-            if (in) {
-                int rec = 0;
-                id = 0;
-#pragma unroll
-                for (int l = 0; l < D; ++l) {
-                    id = id * a.grid[l] + g[l];
-                    rec = rec * nbx[l] + (g[l] - lo[l]);
-                }
+            if (point_locate<D>(s, lo, nbx, i, g, x, id, rec)) {
                 if (id != cur_id) {                        // the point lies in another block: its record
-                    fetch(R, id, rec);
+                    point_fetch<D, C, K, QUANT, IC>(s, staged, s_rec, R, id, rec);
                     cur_id = id;
                 }
                 float wt[K], y[C];
@@ -270,19 +221,9 @@ __global__ void __launch_bounds__(RENDER_THREADS) sample_grad_kernel(SampleGradA
                     bool band = false;
 #pragma unroll
                     for (int l = 0; l < D; ++l) {
-                        float w = 0.0f, dw = 0.0f;
-                        if (s.band[l] > 0.0f) {
-                            const float whi = fminf(fmaxf(0.5f * (1.0f + (x[l] - s.s1[l]) / s.band[l]), 0.0f), 1.0f);
-                            const float wlo = fminf(fmaxf(0.5f * (1.0f + (s.s0[l] - x[l]) / s.band[l]), 0.0f), 1.0f);
-                            w = (whi > 0.0f) ? whi : -wlo;
-                            const float aw = fabsf(w);
-                            dw = (aw > 0.0f && aw < 1.0f) ? ((whi > 0.0f) ? 0.5f : -0.5f) / s.band[l] : 0.0f;
-                        }
-                        sd[l] = (w > 0.0f) ? 1 : -1;
-                        const int gn = g[l] + sd[l];
-                        const bool there = gn >= 0 && gn < a.grid[l];
-                        wn[l] = there ? fabsf(w) : 0.0f;
-                        dwn[l] = there ? dw : 0.0f;
+                        const float w = point_window(s, l, x[l], g[l], sd[l], wn[l]);
+                        // strictly inside (0, 1) and the neighbour inside the grid: +-0.5 / b; clamped or outside: 0
+                        dwn[l] = (wn[l] > 0.0f && wn[l] < 1.0f) ? ((w > 0.0f) ? 0.5f : -0.5f) / s.band[l] : 0.0f;
                         band = band || (wn[l] > 0.0f);
                     }
                     if (band) {
@@ -310,28 +251,22 @@ __global__ void __launch_bounds__(RENDER_THREADS) sample_grad_kernel(SampleGradA
                             for (int l = 0; l < D; ++l) dnum[l][c] = fmaf(dden[l], v[c], den * dv[l][c]);
                         }
 #pragma unroll 1
-                        for (int cm = 1; cm < (1 << D); ++cm) {        // the corners: bit l = the neighbour on axis l
-                            float Wc = 1.0f, dWc[D];
-                            float xn[D];
-                            int nrc = 0;
-                            long long nid = 0;
+                        for (int cm = 1; cm < (1 << D); ++cm) {
+                            float xn[D], dWc[D];
+                            int nrc;
+                            long long nid;
+                            const float Wc = point_corner<D>(s, lo, nbx, cm, g, x, sd, wn, xn, nid, nrc);
 #pragma unroll
-                            for (int l = 0; l < D; ++l) {
-                                const bool nb = ((cm >> l) & 1) != 0;
-                                const int gg = g[l] + (nb ? sd[l] : 0);
-                                Wc *= nb ? wn[l] : 1.0f - wn[l];
-                                xn[l] = nb ? x[l] - (float)sd[l] * s.pitch[l] : x[l];
-                                nid = nid * a.grid[l] + gg;
-                                nrc = nrc * nbx[l] + (gg - lo[l]);
-                                float dW = nb ? dwn[l] : -dwn[l];
+                            for (int l = 0; l < D; ++l) {      // the product rule
+                                float dW = (((cm >> l) & 1) != 0) ? dwn[l] : -dwn[l];
 #pragma unroll
                                 for (int m = 0; m < D; ++m)
                                     if (m != l) dW *= (((cm >> m) & 1) != 0) ? wn[m] : 1.0f - wn[m];
                                 dWc[l] = dW;
                             }
-                            if (Wc > 0.0f) {               // (weight 0: its slopes are 0 too, and nid / nrc are not used)
+                            if (Wc > 0.0f) {               // (weight 0: its slopes are 0 too)
                                 BlockRegs<D, C, K> N;
-                                fetch(N, nid, nrc);
+                                point_fetch<D, C, K, QUANT, IC>(s, staged, s_rec, N, nid, nrc);
                                 float wtn[K], yn[C], vn[C], dvn[D][C];
                                 grad_eval<D, C, K, IC>(N, a.kc, xn, wtn, yn, dvn);
                                 if (has_influence<K>(wtn)) {
@@ -379,41 +314,18 @@ __global__ void __launch_bounds__(RENDER_THREADS) sample_grad_kernel(SampleGradA
         }
     }
     __syncthreads();
-    // the workgroup's run of every plane
-    for (int plane = 0; plane < 3; ++plane) {
-        if (plane == 1 && q.values == nullptr) continue;
-        if (plane == 2 && s.block == nullptr) continue;
-        const int cps = (plane == 0) ? D * C : ((plane == 1) ? C : 1);
-        const int vs = ((plane == 0) ? q.vec_jac : ((plane == 1) ? q.vec_val : s.vec_blk)) ? 2 : 0;
-        const int cpr = ((per * cps + (1 << vs) - 1) >> vs) + 1;           // 16-byte lines the run can touch
-        const long long e0 = p0 * cps, e1 = pe * cps;
-        for (int ch = tid; ch < cpr; ch += RENDER_THREADS) {
-            if (plane == 2) render_store_run<false>(sbk, s.block, e0, e1, 0, vs, ch);
-            else if (plane == 1) render_store_run<false>(sv, q.values, e0, e1, 0, vs, ch);
-            else render_store_run<false>(sj, q.jac, e0, e1, 0, vs, ch);
-        }
-    }
+    point_store_plane<SAMPLE_GRAD_PPL>(p0, pe, sj, q.jac, D * C, q.vec_jac ? 2 : 0, false);
+    if (q.values != nullptr) point_store_plane<SAMPLE_GRAD_PPL>(p0, pe, sv, q.values, C, q.vec_val ? 2 : 0, false);
+    if (s.block != nullptr) point_store_plane<SAMPLE_GRAD_PPL>(p0, pe, sbk, s.block, 1, s.vec_blk ? 2 : 0, false);
 }
 
-// The launch geometry and the LDS carve-up for checked arguments: pure host code.  The record budget, the box and the
-// offsets are sample_layout's (the staging it adds to its own total is smaller than this kernel's, so its 160 KB test never
-// binds first); the staging and the workgroups are this kernel's.
-inline hipError_t sample_grad_layout(int D, int C, int rec_floats, long long records, SampleGradArgs& q, RenderLayout& g) {
-    const hipError_t e = sample_layout(D, C, rec_floats, records, q.s, g);
-    if (e != hipSuccess) return e;
-    const long long per = (long long)SAMPLE_GRAD_PPL * RENDER_THREADS;
-    g.hl = 0;
-    g.lds_bytes = sizeof(float) * ((size_t)q.s.r.off_stage + (size_t)per * (D * C + C + 1));
-    if (g.lds_bytes > 160u * 1024u) return hipErrorNotSupported;
-    g.workgroups = (q.s.num_points + per - 1) / per;
-    if (g.workgroups > 0x7fffffffLL) return hipErrorNotSupported;
-    return hipSuccess;
-}
-
+// The launch geometry and the LDS carve-up for checked arguments (point_layout): a point stages its Jacobian, its values and
+// its block; there is no hoisting level.
 template <int D, int C, int K, bool FULL>
 hipError_t sample_grad_layout(SampleGradArgs& q, long long records, RenderLayout& g) {
     if (q.s.r.kc.qmode != 0 && !FULL) return hipErrorNotSupported;
-    return sample_grad_layout(D, C, BlendRec<D, C, K>::STRIDE, records, q, g);
+    g.hl = 0;
+    return point_layout(D, D * C + C + 1, SAMPLE_GRAD_PPL, BlendRec<D, C, K>::STRIDE, records, q.s, g);
 }
 
 // the instantiation for (fake-quantised graph, inverse covariance); the fake-quantised ones exist for FULL triples

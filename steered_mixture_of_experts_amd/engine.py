@@ -5,6 +5,7 @@ stream.  All arithmetic happens in libsmoe_hip.so; there is no eager/PyTorch fal
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import dataclasses
 from typing import Dict, Optional, Sequence
@@ -202,6 +203,17 @@ class _Engine:
         am = torch.full(tuple(extent), none, dtype=id_dtype, device=self.device) if want_argmax else None
         return out, (_lib.SMOE_IMAGE_U8 if dtype == torch.uint8 else _lib.SMOE_IMAGE_F32), am
 
+    def _blend_list(self, who, blend):
+        """``blend`` as one float per axis (a single value stands for every axis), or None."""
+        if blend is None:
+            return None
+        d = self.cfg.dim
+        bl = [float(v) for v in np.atleast_1d(blend)]
+        bl = bl * d if len(bl) == 1 else bl
+        if len(bl) != d:
+            raise ValueError(f"{who}: blend needs one value or {d}")
+        return bl
+
     @staticmethod
     def _axis_slots(axes):
         return _slots(C.c_void_p, [t.data_ptr() for t in axes], None)
@@ -309,15 +321,10 @@ class BlockEngine(_Engine):
                 blend=None):
         """``render`` and ``render_blend``: ``who`` names the method in the messages, ``entry`` is its C entry point.
         ``covered``: the blocks ``params`` and ``active`` hold; ``B``: the blocks to render; ``blend``: render_blend's."""
-        d = self.cfg.dim
         self._check_params(params, covered)
         self._check_render_arity(who, dtype, axes, (grid, extent), "axes, grid and extent")
         self._check_axis_tables(who, axes)
-        if blend is not None:
-            bl = [float(v) for v in np.atleast_1d(blend)]
-            bl = bl * d if len(bl) == 1 else bl
-            if len(bl) != d:
-                raise ValueError(f"{who}: blend needs one value or {d}")
+        bl = self._blend_list(who, blend)
         grid = [int(g) for g in grid]
         extent = [int(e) for e in extent]
         total = 1
@@ -359,16 +366,10 @@ class BlockEngine(_Engine):
         for g in grid:
             total *= int(g)
         B = total - int(first_block) if num_blocks is None else int(num_blocks)
-        held = getattr(self, "_center_grid", None)
 
-        def entry(*args):                                    # the image-wide centre grid around the launch alone
-            if center_grid is not None:
-                self.set_center_grid(center_grid)
-            try:
+        def entry(*args):
+            with self._center_grid_installed(center_grid):
                 return self.lib.smoe_render_blend(*args)
-            finally:
-                if center_grid is not None:
-                    self.set_center_grid(held)
         return self._render("render_blend", entry, params, active, total, axes, grid, extent, first_block, B, out, dtype,
                             want_argmax, blend)
 
@@ -380,7 +381,6 @@ class BlockEngine(_Engine):
         device table of the ``E_l`` coordinates in block units (``blocks.view_axis`` makes both).  ``params``, ``active`` and
         ``center_grid`` cover ALL ``prod(grid)`` blocks, as in ``render_blend``; ``blend``: None or render_blend's.  Returns
         the image, with ``want_argmax`` also the uint8 map of the own block's kernel ids (255: none)."""
-        d = self.cfg.dim
         who = "render_view"
         grid = [int(g) for g in grid]
         view_first = [int(g) for g in view_first]
@@ -398,43 +398,35 @@ class BlockEngine(_Engine):
         if min(extent) < 1:
             raise ValueError(f"{who}: every axis needs at least one sample")
         self._check_axis_tables(who, axes, extent)
-        bl = None
-        if blend is not None:
-            bl = [float(v) for v in np.atleast_1d(blend)]
-            bl = bl * d if len(bl) == 1 else bl
-            if len(bl) != d:
-                raise ValueError(f"{who}: blend needs one value or {d}")
+        bl = self._blend_list(who, blend)
         out, fmt, am = self._render_planes(out, extent, dtype, True, want_argmax, 255, torch.uint8)
         cp = self._cparams(params)
-        held = getattr(self, "_center_grid", None)
-        if center_grid is not None:                          # the image-wide centre grid around the launch alone
-            self.set_center_grid(center_grid)
-        try:
+        with self._center_grid_installed(center_grid):
             rc = self.lib.smoe_render_view(
                 self._h, C.byref(cp), _ptr(active), _slots(C.c_int32, grid, 1), _slots(C.c_int32, view_first, 0),
                 _slots(C.c_int32, [t.size - 1 for t in st], 1), _slots(C.c_void_p, [t.ctypes.data for t in st], None),
                 self._axis_slots(axes), None if bl is None else _slots(C.c_float, bl, 0.0), _ptr(out), fmt, _ptr(am),
                 self._stream())
-        finally:
-            if center_grid is not None:
-                self.set_center_grid(held)
         _lib.check(rc)
         return (out, am) if want_argmax else out
 
-    def sample(self, params, active, grid, length, points, blend=None, out=None, dtype=torch.float32, want_argmax=False,
-               want_block=False, center_grid=None):
-        """Point decode (include/smoe_hip.h: smoe_sample): the model at the positions ``points`` -- a contiguous float32 device
-        tensor ``[N, d]`` in source pixels (``blocks.point_blocks`` states the mapping) -- into ``[N, C]``.  ``length``: the
-        true extent of the image in pixels per axis.  ``params``, ``active`` and ``center_grid`` cover ALL ``prod(grid)``
-        blocks, as in ``render_view``; ``blend``: None or render_blend's.  Points outside the image give 0.  Returns the
-        values, then with ``want_argmax`` the uint8 local kernel ids of the own block ``[N]`` (255: none or outside) and with
-        ``want_block`` the int32 image-wide block indices ``[N]`` (-1: outside)."""
+    @contextlib.contextmanager
+    def _center_grid_installed(self, center_grid):
+        """The image-wide centre grid (or None: nothing to do) around a launch alone: what the engine held is put back."""
+        if center_grid is None:
+            yield
+            return
+        held = getattr(self, "_center_grid", None)
+        self.set_center_grid(center_grid)
+        try:
+            yield
+        finally:
+            self.set_center_grid(held)
+
+    def _check_point_args(self, who, params, active, grid, length, points, blend):
+        """The arguments ``sample`` and ``sample_grad`` share, checked (``grid`` and ``length``: lists of int).  Returns the
+        number of points and the blend as one float per axis (or None)."""
         d = self.cfg.dim
-        who = "sample"
-        grid = [int(g) for g in grid]
-        length = [int(v) for v in length]
-        if dtype not in (torch.float32, torch.uint8):
-            raise ValueError(f"{who}: dtype must be torch.float32 or torch.uint8")
         if len(grid) != d or len(length) != d:
             raise ValueError(f"{who}: grid and length need {d} entries")
         total = 1
@@ -446,32 +438,39 @@ class BlockEngine(_Engine):
         if points.dim() != 2 or points.shape[1] != d or points.dtype != torch.float32 or not points.is_contiguous() \
                 or points.device != self.device:
             raise ValueError(f"{who}: points must be a contiguous float32 tensor [N, {d}] on {self.device}")
-        N = int(points.shape[0])
-        bl = None
-        if blend is not None:
-            bl = [float(v) for v in np.atleast_1d(blend)]
-            bl = bl * d if len(bl) == 1 else bl
-            if len(bl) != d:
-                raise ValueError(f"{who}: blend needs one value or {d}")
-        shape = (N, self.cfg.channels)
+        bl = self._blend_list(who, blend)
+        return int(points.shape[0]), bl
+
+    def _point_out(self, who, out, shape, dtype, dtype_name):
+        """``out`` checked against ``shape`` and ``dtype`` (``dtype_name``: its wording in the message), or a new tensor."""
         if out is None:
-            out = torch.empty(shape, dtype=dtype, device=self.device)
-        elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or out.device != self.device:
-            raise ValueError(f"{who}: out must be a contiguous {dtype} tensor {shape} on {self.device}")
+            return torch.empty(shape, dtype=dtype, device=self.device)
+        if tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"{who}: out must be a contiguous {dtype_name} tensor {shape} on {self.device}")
+        return out
+
+    def sample(self, params, active, grid, length, points, blend=None, out=None, dtype=torch.float32, want_argmax=False,
+               want_block=False, center_grid=None):
+        """Point decode (include/smoe_hip.h: smoe_sample): the model at the positions ``points`` -- a contiguous float32 device
+        tensor ``[N, d]`` in source pixels (``blocks.point_blocks`` states the mapping) -- into ``[N, C]``.  ``length``: the
+        true extent of the image in pixels per axis.  ``params``, ``active`` and ``center_grid`` cover ALL ``prod(grid)``
+        blocks, as in ``render_view``; ``blend``: None or render_blend's.  Points outside the image give 0.  Returns the
+        values, then with ``want_argmax`` the uint8 local kernel ids of the own block ``[N]`` (255: none or outside) and with
+        ``want_block`` the int32 image-wide block indices ``[N]`` (-1: outside)."""
+        who = "sample"
+        grid, length = [int(g) for g in grid], [int(v) for v in length]
+        if dtype not in (torch.float32, torch.uint8):
+            raise ValueError(f"{who}: dtype must be torch.float32 or torch.uint8")
+        N, bl = self._check_point_args(who, params, active, grid, length, points, blend)
+        out = self._point_out(who, out, (N, self.cfg.channels), dtype, dtype)
         fmt = _lib.SMOE_IMAGE_U8 if dtype == torch.uint8 else _lib.SMOE_IMAGE_F32
         am = torch.empty((N,), dtype=torch.uint8, device=self.device) if want_argmax else None
         bk = torch.empty((N,), dtype=torch.int32, device=self.device) if want_block else None
         cp = self._cparams(params)
-        held = getattr(self, "_center_grid", None)
-        if center_grid is not None:                          # the image-wide centre grid around the launch alone
-            self.set_center_grid(center_grid)
-        try:
+        with self._center_grid_installed(center_grid):
             rc = self.lib.smoe_sample(self._h, C.byref(cp), _ptr(active), _slots(C.c_int32, grid, 1), _slots(C.c_int32, length, 1),
                                       _ptr(points), N, None if bl is None else _slots(C.c_float, bl, 0.0), _ptr(out), fmt,
                                       _ptr(am), _ptr(bk), self._stream())
-        finally:
-            if center_grid is not None:
-                self.set_center_grid(held)
         _lib.check(rc)
         res = (out,) + ((am,) if want_argmax else ()) + ((bk,) if want_block else ())
         return res if len(res) > 1 else out
@@ -483,47 +482,18 @@ class BlockEngine(_Engine):
         ``jac[i, l, c] = dV_c / dx_l`` per source pixel, of the value before the lattice.  Points outside the image give 0.
         Returns the Jacobian, then with ``want_values`` the float32 values before the lattice ``[N, C]`` and with
         ``want_block`` the int32 image-wide block indices ``[N]`` (-1: outside)."""
-        d = self.cfg.dim
         who = "sample_grad"
-        grid = [int(g) for g in grid]
-        length = [int(v) for v in length]
-        if len(grid) != d or len(length) != d:
-            raise ValueError(f"{who}: grid and length need {d} entries")
-        total = 1
-        for g in grid:
-            total *= g
-        self._check_params(params, total)
-        if active is not None and (tuple(active.shape) != (total,) or active.dtype != torch.int32 or active.device != self.device):
-            raise ValueError(f"{who}: active must be int32 [{total}] on {self.device}")
-        if points.dim() != 2 or points.shape[1] != d or points.dtype != torch.float32 or not points.is_contiguous() \
-                or points.device != self.device:
-            raise ValueError(f"{who}: points must be a contiguous float32 tensor [N, {d}] on {self.device}")
-        N = int(points.shape[0])
-        bl = None
-        if blend is not None:
-            bl = [float(v) for v in np.atleast_1d(blend)]
-            bl = bl * d if len(bl) == 1 else bl
-            if len(bl) != d:
-                raise ValueError(f"{who}: blend needs one value or {d}")
-        shape = (N, d, self.cfg.channels)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=self.device)
-        elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
-            raise ValueError(f"{who}: out must be a contiguous float32 tensor {shape} on {self.device}")
+        grid, length = [int(g) for g in grid], [int(v) for v in length]
+        N, bl = self._check_point_args(who, params, active, grid, length, points, blend)
+        out = self._point_out(who, out, (N, self.cfg.dim, self.cfg.channels), torch.float32, "float32")
         val = torch.empty((N, self.cfg.channels), dtype=torch.float32, device=self.device) if want_values else None
         bk = torch.empty((N,), dtype=torch.int32, device=self.device) if want_block else None
         cp = self._cparams(params)
-        held = getattr(self, "_center_grid", None)
-        if center_grid is not None:                          # the image-wide centre grid around the launch alone
-            self.set_center_grid(center_grid)
-        try:
+        with self._center_grid_installed(center_grid):
             rc = self.lib.smoe_sample_grad(self._h, C.byref(cp), _ptr(active), _slots(C.c_int32, grid, 1),
                                            _slots(C.c_int32, length, 1), _ptr(points), N,
                                            None if bl is None else _slots(C.c_float, bl, 0.0), _ptr(out), _ptr(val), _ptr(bk),
                                            self._stream())
-        finally:
-            if center_grid is not None:
-                self.set_center_grid(held)
         _lib.check(rc)
         res = (out,) + ((val,) if want_values else ()) + ((bk,) if want_block else ())
         return res if len(res) > 1 else out

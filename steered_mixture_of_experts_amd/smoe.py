@@ -796,16 +796,8 @@ class Smoe(_SmoeBase):
         ``get_weight_matrix_argmax``; -1 where no kernel has influence on the sample).  ``to_host=False`` returns device
         tensors.  Several ranks: every rank renders its blocks and the images are summed; the result is the same on
         every rank and for every number of ranks."""
-        d = self.dim_domain
-        bl = [float(v) for v in np.atleast_1d(blend)]
-        bl = bl * d if len(bl) == 1 else bl
-        if len(bl) != d:
-            raise ValueError(f"render: blend needs one value or {d}")
-        for v, nl in zip(bl, self.batch_size_valued):
-            if not np.isfinite(v) or v < 0 or v > nl / 2:
-                raise ValueError("render: blend must lie within 0 .. block size / 2 on every axis")
-        return self._render(scale, samples_per_block, dtype, quantized, want_argmax, to_host,
-                            blend=bl if any(v > 0 for v in bl) else None)
+        bl = self._blend_arg("render", blend)
+        return self._render(scale, samples_per_block, dtype, quantized, want_argmax, to_host, blend=bl)
 
     def render_view(self, window, size=None, scale=None, dtype=np.float32, quantized=False, want_argmax=False,
                     to_host=True, blend=0.0):
@@ -821,13 +813,7 @@ class Smoe(_SmoeBase):
         and every rank renders the whole view (a view is small); the result is the same on every rank and for every
         number of ranks."""
         d, n = self.dim_domain, self.batch_size_valued
-        bl = [float(v) for v in np.atleast_1d(blend)]
-        bl = bl * d if len(bl) == 1 else bl
-        if len(bl) != d:
-            raise ValueError(f"render_view: blend needs one value or {d}")
-        for v, nl in zip(bl, n):
-            if not np.isfinite(v) or v < 0 or v > nl / 2:
-                raise ValueError("render_view: blend must lie within 0 .. block size / 2 on every axis")
+        bl = self._blend_arg("render_view", blend)
         window = [None] * d if window is None else list(window)
         if len(window) != d:
             raise ValueError(f"render_view: window needs one (lo, hi) per axis ({d})")
@@ -859,7 +845,7 @@ class Smoe(_SmoeBase):
         tabs = [blk.view_axis(n[l], self.grid[l], self.image.shape[l], win[l][0], win[l][1], E[l]) for l in range(d)]
         params, active, center = self._whole_model(quantized)
         res = eng.render_view(params, active, self.grid, [t[0] for t in tabs], [t[2] for t in tabs],
-                              [torch.from_numpy(t[3]).to(dev) for t in tabs], blend=bl if any(v > 0 for v in bl) else None,
+                              [torch.from_numpy(t[3]).to(dev) for t in tabs], blend=bl,
                               dtype=tdt, want_argmax=want_argmax, center_grid=center)
         img, ids = res if want_argmax else (res, None)
         if ids is not None:
@@ -890,6 +876,28 @@ class Smoe(_SmoeBase):
                                                                dtype=np.float32)).to(dev)
         return params, active, center
 
+    def _blend_arg(self, who, blend):
+        """``blend`` of ``render``, ``render_view``, ``sample`` and ``sample_grad`` (a number or one per axis, source pixels,
+        ``0 .. n_l / 2``) as the engine takes it: one float per axis, or None where no axis blends."""
+        d = self.dim_domain
+        bl = [float(v) for v in np.atleast_1d(blend)]
+        bl = bl * d if len(bl) == 1 else bl
+        if len(bl) != d:
+            raise ValueError(f"{who}: blend needs one value or {d}")
+        for v, nl in zip(bl, self.batch_size_valued):
+            if not np.isfinite(v) or v < 0 or v > nl / 2:
+                raise ValueError(f"{who}: blend must lie within 0 .. block size / 2 on every axis")
+        return bl if any(v > 0 for v in bl) else None
+
+    def _points_arg(self, who, points, dev):
+        """``points`` ``[..., d]`` (array-like or a tensor) as the engine takes them -- a contiguous float32 ``[N, d]`` tensor on
+        ``dev`` -- and their leading shape."""
+        d = self.dim_domain
+        pts = points if torch.is_tensor(points) else torch.from_numpy(np.ascontiguousarray(np.asarray(points), dtype=np.float32))
+        if pts.dim() < 1 or pts.shape[-1] != d:
+            raise ValueError(f"{who}: points need a trailing axis of {d} coordinates")
+        return pts.to(device=dev, dtype=torch.float32).reshape(-1, d).contiguous(), tuple(pts.shape[:-1])
+
     def sample(self, points, dtype=np.float32, quantized=False, want_argmax=False, to_host=True, blend=0.0):
         """The model's value at arbitrary positions, on the device (the engine's ``sample``; include/smoe_hip.h: smoe_sample):
         a rotated or warped view, a motion-compensated lookup, a profile along a line, a few thousand probes -- no pixel is
@@ -900,14 +908,8 @@ class Smoe(_SmoeBase):
         (int64; -1: no kernel has influence, or outside).  The pixel centres ``q + 0.5`` give ``render()`` bit for bit.
         ``to_host=False`` returns device tensors.  Several ranks: parameters and lists are gathered and every rank evaluates
         all points; the result is the same on every rank and for every number of ranks."""
-        d, n = self.dim_domain, self.batch_size_valued
-        bl = [float(v) for v in np.atleast_1d(blend)]
-        bl = bl * d if len(bl) == 1 else bl
-        if len(bl) != d:
-            raise ValueError(f"sample: blend needs one value or {d}")
-        for v, nl in zip(bl, n):
-            if not np.isfinite(v) or v < 0 or v > nl / 2:
-                raise ValueError("sample: blend must lie within 0 .. block size / 2 on every axis")
+        d = self.dim_domain
+        bl = self._blend_arg("sample", blend)
         npdt = np.dtype(dtype)
         if npdt not in (np.dtype(np.float32), np.dtype(np.uint8)):
             raise ValueError("sample: dtype must be float32 or uint8")
@@ -916,15 +918,10 @@ class Smoe(_SmoeBase):
         if not hasattr(eng, "sample"):
             raise NotImplementedError("this engine has no sample()")
         dev = eng.device
-        pts = points if torch.is_tensor(points) else torch.from_numpy(np.ascontiguousarray(np.asarray(points), dtype=np.float32))
-        if pts.dim() < 1 or pts.shape[-1] != d:
-            raise ValueError(f"sample: points need a trailing axis of {d} coordinates")
-        lead = tuple(pts.shape[:-1])
-        pts = pts.to(device=dev, dtype=torch.float32).reshape(-1, d).contiguous()
+        pts, lead = self._points_arg("sample", points, dev)
         params, active, center = self._whole_model(quantized)
         res = eng.sample(params, active, self.grid, [int(v) for v in self.image.shape[:d]], pts,
-                         blend=bl if any(v > 0 for v in bl) else None, dtype=tdt, want_argmax=want_argmax,
-                         want_block=want_argmax, center_grid=center)
+                         blend=bl, dtype=tdt, want_argmax=want_argmax, want_block=want_argmax, center_grid=center)
         img, ids = (res[0], res[1:]) if want_argmax else (res, None)
         img = img.reshape(lead + (self.channels,))
         if ids is not None:
@@ -950,26 +947,16 @@ class Smoe(_SmoeBase):
         ``quantized``, ``blend`` and the kernel lists are ``sample``'s.  Returns ``[..., d, C]`` float32,
         ``jac[..., l, c] = dV_c / dx_l`` per source pixel (0 outside the image); with ``want_values`` also the float32
         values before the lattice ``[..., C]``.  ``to_host=False`` returns device tensors.  Several ranks: as ``sample``."""
-        d, n = self.dim_domain, self.batch_size_valued
-        bl = [float(v) for v in np.atleast_1d(blend)]
-        bl = bl * d if len(bl) == 1 else bl
-        if len(bl) != d:
-            raise ValueError(f"sample_grad: blend needs one value or {d}")
-        for v, nl in zip(bl, n):
-            if not np.isfinite(v) or v < 0 or v > nl / 2:
-                raise ValueError("sample_grad: blend must lie within 0 .. block size / 2 on every axis")
+        d = self.dim_domain
+        bl = self._blend_arg("sample_grad", blend)
         eng = self._engine
         if not hasattr(eng, "sample_grad"):
             raise NotImplementedError("this engine has no sample_grad()")
         dev = eng.device
-        pts = points if torch.is_tensor(points) else torch.from_numpy(np.ascontiguousarray(np.asarray(points), dtype=np.float32))
-        if pts.dim() < 1 or pts.shape[-1] != d:
-            raise ValueError(f"sample_grad: points need a trailing axis of {d} coordinates")
-        lead = tuple(pts.shape[:-1])
-        pts = pts.to(device=dev, dtype=torch.float32).reshape(-1, d).contiguous()
+        pts, lead = self._points_arg("sample_grad", points, dev)
         params, active, center = self._whole_model(quantized)
         res = eng.sample_grad(params, active, self.grid, [int(v) for v in self.image.shape[:d]], pts,
-                              blend=bl if any(v > 0 for v in bl) else None, want_values=want_values, center_grid=center)
+                              blend=bl, want_values=want_values, center_grid=center)
         jac, val = res if want_values else (res, None)
         jac = jac.reshape(lead + (d, self.channels))
         if val is not None:
