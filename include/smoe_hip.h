@@ -544,6 +544,48 @@ int smoe_shared_render_view(smoe_shared_handle h, const smoe_params* p, const ui
                             const int32_t* const axis_batch[3],
                             void* image, int32_t image_format, int32_t* argmax, void* stream);
 
+/* Exact spatial derivative of the whole-image model at arbitrary points -- the counterpart of smoe_sample_grad for the
+ * shared-kernel mode, the one model here that is one continuous function without block seams: an edge map, a structure
+ * tensor, dv/dt of a video model, a Gauss-Newton alignment step.  Differences of smoe_shared_sample sit on the 8-bit lattice.
+ *   p, lists, points, num_points   as in smoe_shared_sample
+ *   jac                      DEVICE [num_points, dim, C] fp32: jac[i, l, c] = dv_c / dx_l per source pixel
+ *   values                   DEVICE [num_points, C] fp32 or NULL: v, the value before the lattice
+ *   batch                    DEVICE [num_points] int32 or NULL: global id of the owning batch, -1 outside
+ * Definition.  Points, the outside rule, the owning batch and the image-unit coordinate u are smoe_shared_sample's
+ * (u = (x - 0.5f) / (float)(S - 1), 0 for S == 1).  The evaluated kernels of a point are the compacted list of its batch,
+ * exactly as in smoe_shared_sample (listed, fake-quantised prior > 0, ascending ids; lists == NULL: every kernel; the same
+ * records, mode-3 image-wide ranges and centre grid).  Over them:
+ *   g_k = gate of kernel k at u    S = sum g_k    w_k = g_k * rcp(max(S, 10e-12))    M_k = [w_k > tau]
+ *   e_kc = nu_kc + sum_l Gamma_klc u_l            y_c = sum_k M_k w_k e_kc           v_c = med3(y_c, 0, nudged_max)
+ * The gate and y are formed by the same statements in the same order as smoe_shared_sample forms them, so
+ * floorf(fmaf(v_c, inv_scale, 0.5f)) * scale equals smoe_shared_sample's float image bit for bit.
+ *   s_k = d log g_k / du = -A_k z_k, z_k = A_k^T (u - mu_k)     (train_inverse_cov: s_k = -A_k (u - mu_k), A_k symmetric)
+ *   sbar = sum_j w_j s_j over ALL evaluated kernels, 0 on the floor of the normaliser (S <= 10e-12)
+ *   dy_c / du_l = sum_k M_k w_k ((s_kl - sbar_l) e_kc + Gamma_klc)    (the slopes are centred on sbar before they meet the experts)
+ *   dv = dy where the clip did not act (v_c == y_c), else 0
+ *   jac[i, l, c] = dv_c / du_l / (S_l - 1) per source pixel, 0 on an axis with S_l == 1
+ * Mask, clip and lattice are held piecewise constant.  Outside points give 0 / 0 / -1; an inside point whose batch has an
+ * empty list gives 0 / 0 / its batch id.  A point's three outputs depend on its coordinates, the model and its batch's list
+ * only: not on num_points, its place in the list, the other points or the cut of the launch.
+ * A workgroup takes 512 consecutive points and walks the distinct batches among them as smoe_shared_sample does.
+ * num_points == 0 is a successful no-op.  SMOE_ERR_INVALID names the offending argument: a null handle or p; with
+ * num_points > 0 a null points or jac; num_points < 0.  SMOE_ERR_UNSUPPORTED: image_shape[l] > 2^24, 2^31 or more workgroups,
+ * more than 160 KB of LDS. */
+int smoe_shared_sample_grad(smoe_shared_handle h, const smoe_params* p, const uint32_t* lists,
+                            const float* points, int64_t num_points,
+                            float* jac, float* values, int32_t* batch, void* stream);
+
+/* The same derivative on a dense view given by per-axis tables: extent, axis_coords and axis_batch are
+ * smoe_shared_render_view's (the batch index clamped, nothing outside), jac [E.., dim, C], values [E.., C] or NULL, batch
+ * [E..] or NULL as in smoe_shared_sample_grad.  A sample is evaluated exactly as smoe_shared_sample_grad evaluates a point
+ * with these coordinates in this batch.  SMOE_ERR_INVALID names the offending argument: a null handle, p, extent,
+ * axis_coords, axis_batch, table or jac; extent[l] < 1.  SMOE_ERR_UNSUPPORTED: 2^31 or more workgroups, more than 160 KB of
+ * LDS (no limit on image_shape). */
+int smoe_shared_render_view_grad(smoe_shared_handle h, const smoe_params* p, const uint32_t* lists,
+                                 const int32_t extent[3], const float* const axis_coords[3],
+                                 const int32_t* const axis_batch[3],
+                                 float* jac, float* values, int32_t* batch, void* stream);
+
 /* run_batched(train=True) minus train_op: forward + tf.gradients of the batches, accumulated into
  * the handle's gradient buffer (accum_ops, smoe.py:1150); kernel lists pruned (smoe.py:1763-1766).
  * Summation order: every batch leaves the raw sums of its listed kernels in a row of its own; the buffer is the sum of

@@ -1562,14 +1562,9 @@ int smoe_shared_render(smoe_shared_handle h, int32_t first_batch, int32_t num_ba
                             "more than 2^30 samples per batch");
 }
 
-// What smoe_shared_sample and smoe_shared_render_view share behind their own argument checks: the format checks, the
-// arguments every point source has, the plan, and -- through the host path of smoe_shared_render: abort word, device,
-// image-wide ranges of THIS call's parameters -- the launch.  a: the point source filled in by the caller.
-static int shared_sample_run(smoe_shared_handle h, const std::string& fn, const smoe_params* p, const uint32_t* lists,
-                             smoe::SharedSampleArgs& a, bool grid, void* values, int32_t image_format, int32_t* argmax, void* stream) {
+// the arguments every point source of the shared-mode point decoders has: the model, the lists and the batch geometry
+static void shared_sample_model(smoe_shared_handle h, const smoe_params* p, const uint32_t* lists, smoe::SharedSampleArgs& a) {
     const int D = h->cfg.dim;
-    if (image_format == SMOE_IMAGE_U8 && h->cfg.precision > 8)
-        return fail(SMOE_ERR_UNSUPPORTED, fn + ": SMOE_IMAGE_U8 needs precision <= 8");
     a.p = *p; a.lists = lists;
     for (int l = 0; l < SMOE_MAX_DIM; ++l) {
         a.nbs[l] = (l < D) ? h->cfg.batch_shape[l] : 1;
@@ -1578,17 +1573,86 @@ static int shared_sample_run(smoe_shared_handle h, const std::string& fn, const 
     }
     a.K = h->cfg.kernels; a.KW = h->KW;
     a.qrng = h->d_qrng; a.mus_grid = h->mus_grid;
+}
+
+#if !SMOE_HOST_TEST
+// the host path of smoe_shared_render in front of a launch of the point decoders: abort word, device, image-wide ranges of
+// THIS call's parameters
+static int shared_sample_ready(smoe_shared_handle h, const std::string& fn, const smoe_params* p, void* stream) {
+    const int rc = shared_check_abort(h, fn.c_str());
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(h->cfg.device), "hipSetDevice");
+    HIP_TRY(refresh_ranges(h, p, (hipStream_t)stream), (fn + " ranges").c_str());
+    return SMOE_OK;
+}
+#endif
+
+// The dense view of smoe_shared_render_view / smoe_shared_render_view_grad as a point source: extent and tables checked
+// (h, extent, axis_coords, axis_batch are not null), a.ext / a.ax / a.ab / a.num_points filled.
+static int shared_view_source(smoe_shared_handle h, const std::string& fn, const int32_t extent[3],
+                              const float* const axis_coords[3], const int32_t* const axis_batch[3], smoe::SharedSampleArgs& a) {
+    for (int l = 0; l < SMOE_MAX_DIM; ++l) a.ext[l] = 1;
+    a.num_points = 1;
+    for (int l = 0; l < h->cfg.dim; ++l) {
+        const std::string ax = "[" + std::to_string(l) + "]";
+        if (extent[l] < 1) return fail(SMOE_ERR_INVALID, fn + ": extent" + ax + " must be >= 1");
+        if (!axis_coords[l]) return fail(SMOE_ERR_INVALID, fn + ": axis_coords" + ax + " is null");
+        if (!axis_batch[l]) return fail(SMOE_ERR_INVALID, fn + ": axis_batch" + ax + " is null");
+        a.ext[l] = extent[l]; a.ax[l] = axis_coords[l]; a.ab[l] = axis_batch[l];
+        if (extent[l] > (1LL << 42) / a.num_points)     // (before the product can wrap; the plan draws the exact line)
+            return fail(SMOE_ERR_UNSUPPORTED, fn + ": the view would need 2^31 or more workgroups");
+        a.num_points *= extent[l];
+    }
+    return SMOE_OK;
+}
+
+// What smoe_shared_sample and smoe_shared_render_view share behind their own argument checks: the format checks, the
+// arguments every point source has, the plan, and -- through the host path of smoe_shared_render: abort word, device,
+// image-wide ranges of THIS call's parameters -- the launch.  a: the point source filled in by the caller.
+static int shared_sample_run(smoe_shared_handle h, const std::string& fn, const smoe_params* p, const uint32_t* lists,
+                             smoe::SharedSampleArgs& a, bool grid, void* values, int32_t image_format, int32_t* argmax, void* stream) {
+    const int D = h->cfg.dim;
+    if (image_format == SMOE_IMAGE_U8 && h->cfg.precision > 8)
+        return fail(SMOE_ERR_UNSUPPORTED, fn + ": SMOE_IMAGE_U8 needs precision <= 8");
+    shared_sample_model(h, p, lists, a);
     decoder_planes(a, values, image_format, argmax, h->kc);
     smoe::RenderLayout lay;
     const char* const unsupported = "the launch would need 2^31 or more workgroups, or more than 160 KB of LDS";
     int rc = decoder_launched(fn, smoe::shared_sample_layout(D, h->cfg.channels, a.K, a.num_points, lay), unsupported);
     if (rc != SMOE_OK) return rc;
 #if !SMOE_HOST_TEST
-    rc = shared_check_abort(h, fn.c_str());
+    rc = shared_sample_ready(h, fn, p, stream);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(h->cfg.device), "hipSetDevice");
-    HIP_TRY(refresh_ranges(h, p, (hipStream_t)stream), (fn + " ranges").c_str());
     return decoder_launched(fn, smoe::launch_shared_sample(a, D, h->cfg.channels, grid, lay, (hipStream_t)stream), unsupported);
+#else
+    (void)grid; (void)stream;
+    return SMOE_OK;
+#endif
+}
+
+// The same behind smoe_shared_sample_grad and smoe_shared_render_view_grad: the three planes, the pixel units, the plan and --
+// through the same host path -- the launch.  q.s: the point source filled in by the caller.
+static int shared_sample_grad_run(smoe_shared_handle h, const std::string& fn, const smoe_params* p, const uint32_t* lists,
+                                  smoe::SharedSampleGradArgs& q, bool grid, float* jac, float* values, int32_t* batch, void* stream) {
+    const int D = h->cfg.dim;
+    shared_sample_model(h, p, lists, q.s);
+    q.s.kc = h->kc;
+    q.jac = jac; q.values = values; q.batch = batch;
+    q.vec_jac = ((uintptr_t)jac % 16 == 0) ? 1 : 0;
+    q.vec_val = ((uintptr_t)values % 16 == 0) ? 1 : 0;
+    q.vec_bat = ((uintptr_t)batch % 16 == 0) ? 1 : 0;
+    for (int l = 0; l < SMOE_MAX_DIM; ++l) {
+        const int n = (l < D) ? h->cfg.image_shape[l] : 1;
+        q.du_dx[l] = (n > 1) ? (float)(1.0 / (n - 1)) : 0.0f;
+    }
+    smoe::RenderLayout lay;
+    const char* const unsupported = "the launch would need 2^31 or more workgroups, or more than 160 KB of LDS";
+    int rc = decoder_launched(fn, smoe::shared_sample_grad_layout(D, h->cfg.channels, q.s.K, q.s.num_points, lay), unsupported);
+    if (rc != SMOE_OK) return rc;
+#if !SMOE_HOST_TEST
+    rc = shared_sample_ready(h, fn, p, stream);
+    if (rc) return rc;
+    return decoder_launched(fn, smoe::launch_shared_sample_grad(q, D, h->cfg.channels, grid, lay, (hipStream_t)stream), unsupported);
 #else
     (void)grid; (void)stream;
     return SMOE_OK;
@@ -1628,19 +1692,43 @@ int smoe_shared_render_view(smoe_shared_handle h, const smoe_params* p, const ui
         return fail(SMOE_ERR_INVALID, fn + ": image_format must be SMOE_IMAGE_F32 or SMOE_IMAGE_U8");
     smoe::SharedSampleArgs a;
     std::memset(&a, 0, sizeof a);
-    for (int l = 0; l < SMOE_MAX_DIM; ++l) a.ext[l] = 1;
-    a.num_points = 1;
-    for (int l = 0; l < h->cfg.dim; ++l) {
-        const std::string ax = "[" + std::to_string(l) + "]";
-        if (extent[l] < 1) return fail(SMOE_ERR_INVALID, fn + ": extent" + ax + " must be >= 1");
-        if (!axis_coords[l]) return fail(SMOE_ERR_INVALID, fn + ": axis_coords" + ax + " is null");
-        if (!axis_batch[l]) return fail(SMOE_ERR_INVALID, fn + ": axis_batch" + ax + " is null");
-        a.ext[l] = extent[l]; a.ax[l] = axis_coords[l]; a.ab[l] = axis_batch[l];
-        if (extent[l] > (1LL << 42) / a.num_points)     // (before the product can wrap; the plan draws the exact line)
-            return fail(SMOE_ERR_UNSUPPORTED, fn + ": the view would need 2^31 or more workgroups");
-        a.num_points *= extent[l];
-    }
+    const int rc = shared_view_source(h, fn, extent, axis_coords, axis_batch, a);
+    if (rc) return rc;
     return shared_sample_run(h, fn, p, lists, a, true, image, image_format, argmax, stream);
+}
+
+int smoe_shared_sample_grad(smoe_shared_handle h, const smoe_params* p, const uint32_t* lists, const float* points,
+                            int64_t num_points, float* jac, float* values, int32_t* batch, void* stream) {
+    const std::string fn = "smoe_shared_sample_grad";
+    if (!h) return fail(SMOE_ERR_INVALID, fn + ": null handle");
+    if (!params_ok(p)) return fail(SMOE_ERR_INVALID, fn + ": p (all six parameter tensors) is required");
+    if (num_points < 0) return fail(SMOE_ERR_INVALID, fn + ": num_points must be >= 0");
+    if (num_points == 0) return SMOE_OK;
+    if (!points) return fail(SMOE_ERR_INVALID, fn + ": points is required");
+    if (!jac) return fail(SMOE_ERR_INVALID, fn + ": jac is required");
+    for (int l = 0; l < h->cfg.dim; ++l)
+        if (h->cfg.image_shape[l] > (1 << 24))
+            return fail(SMOE_ERR_UNSUPPORTED, fn + ": image_shape must not exceed 2^24 on any axis (batch origins are exact in fp32)");
+    smoe::SharedSampleGradArgs q;
+    std::memset(&q, 0, sizeof q);
+    q.s.points = points; q.s.num_points = num_points;
+    for (int l = 0; l < SMOE_MAX_DIM; ++l) q.s.ext[l] = 1;
+    return shared_sample_grad_run(h, fn, p, lists, q, false, jac, values, batch, stream);
+}
+
+int smoe_shared_render_view_grad(smoe_shared_handle h, const smoe_params* p, const uint32_t* lists, const int32_t extent[3],
+                                 const float* const axis_coords[3], const int32_t* const axis_batch[3],
+                                 float* jac, float* values, int32_t* batch, void* stream) {
+    const std::string fn = "smoe_shared_render_view_grad";
+    if (!h) return fail(SMOE_ERR_INVALID, fn + ": null handle");
+    if (!params_ok(p)) return fail(SMOE_ERR_INVALID, fn + ": p (all six parameter tensors) is required");
+    if (!extent || !axis_coords || !axis_batch) return fail(SMOE_ERR_INVALID, fn + ": extent, axis_coords and axis_batch are required");
+    if (!jac) return fail(SMOE_ERR_INVALID, fn + ": jac is required");
+    smoe::SharedSampleGradArgs q;
+    std::memset(&q, 0, sizeof q);
+    const int rc = shared_view_source(h, fn, extent, axis_coords, axis_batch, q.s);
+    if (rc) return rc;
+    return shared_sample_grad_run(h, fn, p, lists, q, true, jac, values, batch, stream);
 }
 
 // gather: sum the batches' rows into the gradient buffer right away (what smoe_shared_grad_buffer hands out for the

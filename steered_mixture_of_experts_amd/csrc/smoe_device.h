@@ -349,6 +349,17 @@ struct SharedSampleArgs {
     KernelConsts kc;
 };
 
+// smoe_shared_sample_grad / smoe_shared_render_view_grad (smoe_shared_sample_grad.hip.h): the spatial derivative at the points
+// of `s` (its image / argmax planes are unused), the value before the lattice and the owning batch.
+struct SharedSampleGradArgs {
+    SharedSampleArgs s;
+    float* jac;               // [N, D, C] dv_c / dx_l per source pixel
+    float* values;            // [N, C] the value before the lattice, or null
+    int32_t* batch;           // [N] global batch ids, -1 = outside; or null
+    int vec_jac, vec_val, vec_bat;    // the plane's base is 16-byte aligned: vector stores
+    float du_dx[SMOE_MAX_DIM];        // 1 / (image_shape[l] - 1), 0 for an axis of one pixel
+};
+
 // Per-kernel sum over the batches of the current pass, in a fixed order (lane = batch mod 64 ascending, then a butterfly
 // over the lanes): racc[k][PK] and nact[k] are OVERWRITTEN -- bit-identical from run to run and for every split of the
 // batches of a rank over smoe_shared_accumulate calls.
@@ -430,6 +441,9 @@ hipError_t launch_shared_render(const SharedRenderArgs& a, int D, int C, int num
 hipError_t shared_sample_layout(int D, int C, int K, long long num_points, RenderLayout& g);
 // the launch of a planned call; grid: the dense view of a.ext / a.ax / a.ab instead of the list a.points
 hipError_t launch_shared_sample(const SharedSampleArgs& a, int D, int C, bool grid, const RenderLayout& g, hipStream_t st);
+// the same pair for smoe_shared_sample_grad / smoe_shared_render_view_grad
+hipError_t shared_sample_grad_layout(int D, int C, int K, long long num_points, RenderLayout& g);
+hipError_t launch_shared_sample_grad(const SharedSampleGradArgs& q, int D, int C, bool grid, const RenderLayout& g, hipStream_t st);
 
 const Variant* variants(int* count);
 hipError_t launch_readmit(const ReadmitArgs& a, int D, hipStream_t st);

@@ -1144,6 +1144,8 @@ __global__ void shared_readmit_kernel(SharedReadmitArgs a) {
 #include "smoe_shared_render.hip.h"
 // its point and viewport decoder (shared_sample_kernel, launch_shared_sample)
 #include "smoe_shared_sample.hip.h"
+// and the spatial derivative at the same points (shared_sample_grad_kernel, launch_shared_sample_grad)
+#include "smoe_shared_sample_grad.hip.h"
 
 namespace smoe {
 

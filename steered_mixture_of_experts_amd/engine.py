@@ -681,12 +681,8 @@ class SharedEngine(_Engine):
         with the kernel list of the batch that owns it.  ``lists`` int32 ``[num_batches, KW]`` of ALL batches (only read) or
         None: every kernel.  Points outside the image give 0.  Returns the values, with ``want_argmax`` also the int32 global
         kernel ids ``[N]`` (-1: no kernel has influence, or outside)."""
-        d, who = self.cfg.dim, "sample"
-        if points.dim() != 2 or points.shape[1] != d or points.dtype != torch.float32 or not points.is_contiguous() \
-                or points.device != self.device:
-            raise ValueError(f"{who}: points must be a contiguous float32 tensor [N, {d}] on {self.device}")
-        self._check_all_lists(who, lists)
-        N = int(points.shape[0])
+        who = "sample"
+        N = self._check_points(who, points, lists)
         out, fmt, am = self._dense_planes(who, (N,), out, dtype, want_argmax)
         if N > 0:
             cp = self._cparams(params)
@@ -700,6 +696,25 @@ class SharedEngine(_Engine):
         ``batches[l]`` (int32 device table ``[E_l]`` of batch indices on that axis, ``0 .. grid_l - 1``).  ``lists`` as in
         ``sample``.  Returns the image, with ``want_argmax`` also the int32 global kernel ids ``[*E]`` (-1: none)."""
         who = "render_view"
+        extent = self._check_view(who, dtype, axes, batches, lists)
+        out, fmt, am = self._dense_planes(who, extent, out, dtype, want_argmax)
+        cp = self._cparams(params)
+        _lib.check(self.lib.smoe_shared_render_view(self._h, C.byref(cp), _ptr(lists), _slots(C.c_int32, extent, 1),
+                                                    self._axis_slots(axes), self._axis_slots(batches), _ptr(out), fmt, _ptr(am),
+                                                    self._stream()))
+        return (out, am) if want_argmax else out
+
+    def _check_points(self, who, points, lists):
+        """``points`` and ``lists`` as the point decoders take them; returns N."""
+        d = self.cfg.dim
+        if points.dim() != 2 or points.shape[1] != d or points.dtype != torch.float32 or not points.is_contiguous() \
+                or points.device != self.device:
+            raise ValueError(f"{who}: points must be a contiguous float32 tensor [N, {d}] on {self.device}")
+        self._check_all_lists(who, lists)
+        return int(points.shape[0])
+
+    def _check_view(self, who, dtype, axes, batches, lists):
+        """The tables and ``lists`` as the viewport decoders take them; returns the extent."""
         self._check_render_arity(who, dtype, axes, (batches,), "axes and batches")
         self._check_axis_tables(who, axes)
         extent = [int(t.numel()) for t in axes]
@@ -709,12 +724,47 @@ class SharedEngine(_Engine):
                 raise ValueError(f"{who}: every batch table must be a contiguous 1-d int32 tensor on {self.device} "
                                  f"with as many entries as its axis table ({extent})")
         self._check_all_lists(who, lists)
-        out, fmt, am = self._dense_planes(who, extent, out, dtype, want_argmax)
+        return extent
+
+    def _grad_planes(self, who, shape, out, want_values, want_batch):
+        """The Jacobian plane ``[*shape, d, C]`` (``out`` checked, or a new one), the value plane and the batch plane or None."""
+        full = tuple(shape) + (self.cfg.dim, self.cfg.channels)
+        if out is None:
+            out = torch.empty(full, dtype=torch.float32, device=self.device)
+        elif tuple(out.shape) != full or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"{who}: out must be a contiguous float32 tensor {full} on {self.device}")
+        val = torch.empty(tuple(shape) + (self.cfg.channels,), dtype=torch.float32, device=self.device) if want_values else None
+        bk = torch.empty(tuple(shape), dtype=torch.int32, device=self.device) if want_batch else None
+        return out, val, bk
+
+    def sample_grad(self, params, lists, points, out=None, want_values=False, want_batch=False):
+        """Point derivative (include/smoe_hip.h: smoe_shared_sample_grad): the exact spatial derivative of the model at
+        ``sample``'s points, with ``sample``'s lists, into ``[N, d, C]`` float32: ``jac[i, l, c] = dv_c / dx_l`` per source
+        pixel, of the value before the lattice.  Points outside the image give 0.  Returns the Jacobian, then with
+        ``want_values`` the float32 values before the lattice ``[N, C]`` and with ``want_batch`` the int32 global ids of the
+        owning batches ``[N]`` (-1: outside)."""
+        who = "sample_grad"
+        N = self._check_points(who, points, lists)
+        out, val, bk = self._grad_planes(who, (N,), out, want_values, want_batch)
+        if N > 0:
+            cp = self._cparams(params)
+            _lib.check(self.lib.smoe_shared_sample_grad(self._h, C.byref(cp), _ptr(lists), _ptr(points), N, _ptr(out), _ptr(val),
+                                                        _ptr(bk), self._stream()))
+        res = (out,) + ((val,) if want_values else ()) + ((bk,) if want_batch else ())
+        return res if len(res) > 1 else out
+
+    def render_view_grad(self, params, lists, axes, batches, out=None, want_values=False, want_batch=False):
+        """Viewport derivative (include/smoe_hip.h: smoe_shared_render_view_grad): ``sample_grad`` on the dense view of
+        ``render_view``'s tables, ``[*E, d, C]``; the other planes ``[*E, C]`` and ``[*E]``."""
+        who = "render_view_grad"
+        extent = self._check_view(who, torch.float32, axes, batches, lists)
+        out, val, bk = self._grad_planes(who, extent, out, want_values, want_batch)
         cp = self._cparams(params)
-        _lib.check(self.lib.smoe_shared_render_view(self._h, C.byref(cp), _ptr(lists), _slots(C.c_int32, extent, 1),
-                                                    self._axis_slots(axes), self._axis_slots(batches), _ptr(out), fmt, _ptr(am),
-                                                    self._stream()))
-        return (out, am) if want_argmax else out
+        _lib.check(self.lib.smoe_shared_render_view_grad(self._h, C.byref(cp), _ptr(lists), _slots(C.c_int32, extent, 1),
+                                                         self._axis_slots(axes), self._axis_slots(batches), _ptr(out), _ptr(val),
+                                                         _ptr(bk), self._stream()))
+        res = (out,) + ((val,) if want_values else ()) + ((bk,) if want_batch else ())
+        return res if len(res) > 1 else out
 
     def accumulate(self, target, params, lists, first_batch=0, loss_out=None, sse_out=None):
         nb = lists.shape[0]

@@ -96,6 +96,13 @@ def _fake_quant_fixed(x: torch.Tensor, lb: float, ub: float, bits: int) -> torch
     return torch.floor((cl - nmin.to(x.device)) * (1.0 / scale).to(x.device) + 0.5) * scale.to(x.device) + nmin.to(x.device)
 
 
+def _warp_chain(jac: torch.Tensor, matrix, d: int) -> torch.Tensor:
+    """The chain rule through ``x = M (i + 0.5) + t`` of an affine view, on ``jac``'s device: per output cell
+    ``J_view[..., m, c] = sum_l J[..., l, c] M[l, m]`` from the Jacobian per source pixel."""
+    M = torch.from_numpy(np.ascontiguousarray(np.asarray(matrix, dtype=np.float64)[:, :d], dtype=np.float32)).to(jac.device)
+    return torch.einsum("...lc,lm->...mc", jac, M).contiguous()
+
+
 def _train_loop(m, num_iter, val_iter, ukl_iter, pis_l1, u_l1, callbacks, chunk_limit=None):
     """The iteration / validation / stop logic of ``Smoe.train`` (smoe.py:1485-1603), shared by both facades.  ``m`` supplies
     ``run_batched`` and four hooks: ``_quantize`` (quantize_params [+ rescaler], smoe.py:1498-1505,1539-1545),
@@ -978,9 +985,7 @@ class Smoe(_SmoeBase):
         res = self.sample_grad(blk.warp_points(matrix, size), to_host=False, **options)
         jac, val = res if want_values else (res, None)
         if wrt == "view":
-            d = self.dim_domain
-            M = torch.from_numpy(np.ascontiguousarray(np.asarray(matrix, dtype=np.float64)[:, :d], dtype=np.float32)).to(jac.device)
-            jac = torch.einsum("...lc,lm->...mc", jac, M).contiguous()
+            jac = _warp_chain(jac, matrix, self.dim_domain)
         if to_host:
             jac = jac.cpu().numpy()
             val = None if val is None else val.cpu().numpy()
@@ -1340,6 +1345,15 @@ class SharedSmoe(_SmoeBase):
             ids = None if ids is None else ids.cpu().numpy()
         return (img, ids) if want_argmax else img
 
+    def _eval_points_arg(self, who, points, dev):
+        """``points`` ``[..., d]`` (array-like or a tensor) as the engine takes them -- a contiguous float32 ``[N, d]`` tensor on
+        ``dev`` -- and their leading shape."""
+        d = self.dim_domain
+        pts = points if torch.is_tensor(points) else torch.from_numpy(np.ascontiguousarray(np.asarray(points), dtype=np.float32))
+        if pts.dim() < 1 or pts.shape[-1] != d:
+            raise ValueError(f"{who}: points need a trailing axis of {d} coordinates")
+        return pts.to(device=dev, dtype=torch.float32).reshape(-1, d).contiguous(), tuple(pts.shape[:-1])
+
     def eval_points(self, points, dtype=np.float32, quantized=False, want_argmax=False, to_host=True, use_lists=True):
         """The model's value at arbitrary positions, on the device (the engine's ``sample``; include/smoe_hip.h:
         smoe_shared_sample) -- ``Smoe.sample`` for a whole-image model: a rotated or warped view, a profile along a line, a
@@ -1354,18 +1368,45 @@ class SharedSmoe(_SmoeBase):
         rank evaluates all points; the result is the same on every rank and for every number of ranks.
         Neighbouring points are cheap, scattered ones are not: the device walks the distinct batches among 1024 consecutive
         points one after the other."""
-        d = self.dim_domain
         tdt, eng, params, lists = self._eval_model("eval_points", dtype, quantized, use_lists, "sample")
-        pts = points if torch.is_tensor(points) else torch.from_numpy(np.ascontiguousarray(np.asarray(points), dtype=np.float32))
-        if pts.dim() < 1 or pts.shape[-1] != d:
-            raise ValueError(f"eval_points: points need a trailing axis of {d} coordinates")
-        lead = tuple(pts.shape[:-1])
-        pts = pts.to(device=eng.device, dtype=torch.float32).reshape(-1, d).contiguous()
+        pts, lead = self._eval_points_arg("eval_points", points, eng.device)
         res = eng.sample(params, lists, pts, dtype=tdt, want_argmax=want_argmax)
         img, ids = res if want_argmax else (res, None)
         img = img.reshape(lead + (self.channels,))
         ids = None if ids is None else ids.reshape(lead)
         return self._eval_result((img, ids) if want_argmax else img, want_argmax, to_host)
+
+    def _view_tables(self, who, window, size, scale):
+        """``eval_view``'s window / size / scale, checked, as the engine's tables (numpy): per axis the coordinates and the
+        batch indices of the ``E_l`` samples (``blocks.view_axis``)."""
+        d, n = self.dim_domain, self.batch_size_valued
+        shape = [int(v) for v in self.image.shape[:d]]
+        window = [None] * d if window is None else list(window)
+        if len(window) != d:
+            raise ValueError(f"{who}: window needs one (lo, hi) per axis ({d})")
+        win = [(0.0, float(shape[l])) if w is None else (float(w[0]), float(w[1])) for l, w in enumerate(window)]
+        for l, (lo, hi) in enumerate(win):
+            if not (0.0 <= lo < hi <= float(shape[l])):
+                raise ValueError(f"{who}: window[{l}] must satisfy 0 <= lo < hi <= {shape[l]}")
+        if size is not None and scale is not None:
+            raise ValueError(f"{who}: give size or scale, not both")
+        if size is not None:
+            E = [int(v) for v in np.atleast_1d(size)]
+            E = E * d if len(E) == 1 else E
+            if len(E) != d or min(E) < 1:
+                raise ValueError(f"{who}: size needs {d} entries >= 1")
+        else:
+            sc = list(np.atleast_1d(1 if scale is None else scale))
+            sc = sc * d if len(sc) == 1 else sc
+            if len(sc) != d:
+                raise ValueError(f"{who}: scale needs one value or {d}")
+            E = [max(1, int(round((hi - lo) * float(v)))) for (lo, hi), v in zip(win, sc)]
+        axes, batches = [], []
+        for l in range(d):
+            axes.append(blk.view_axis(shape[l], 1, shape[l], win[l][0], win[l][1], E[l])[3])
+            first, nblocks, start, _ = blk.view_axis(n[l], shape[l] // n[l], shape[l], win[l][0], win[l][1], E[l])
+            batches.append((first + np.repeat(np.arange(nblocks), np.diff(start))).astype(np.int32))
+        return axes, batches
 
     def eval_view(self, window, size=None, scale=None, dtype=np.float32, quantized=False, want_argmax=False,
                   to_host=True, use_lists=True):
@@ -1379,37 +1420,10 @@ class SharedSmoe(_SmoeBase):
         ``blocks.view_axis(S, 1, S, lo, hi, E)[3]`` on the image axis of ``S`` pixels, its batch the one of
         ``blocks.view_axis(n, grid_l, S, lo, hi, E)`` -- a window that is a crop of a ``render`` grid gives exactly that
         crop.  The other options and the return value are ``eval_points``'s, ``[*E, C]``."""
-        d, n = self.dim_domain, self.batch_size_valued
-        shape = [int(v) for v in self.image.shape[:d]]
-        window = [None] * d if window is None else list(window)
-        if len(window) != d:
-            raise ValueError(f"eval_view: window needs one (lo, hi) per axis ({d})")
-        win = [(0.0, float(shape[l])) if w is None else (float(w[0]), float(w[1])) for l, w in enumerate(window)]
-        for l, (lo, hi) in enumerate(win):
-            if not (0.0 <= lo < hi <= float(shape[l])):
-                raise ValueError(f"eval_view: window[{l}] must satisfy 0 <= lo < hi <= {shape[l]}")
-        if size is not None and scale is not None:
-            raise ValueError("eval_view: give size or scale, not both")
-        if size is not None:
-            E = [int(v) for v in np.atleast_1d(size)]
-            E = E * d if len(E) == 1 else E
-            if len(E) != d or min(E) < 1:
-                raise ValueError(f"eval_view: size needs {d} entries >= 1")
-        else:
-            sc = list(np.atleast_1d(1 if scale is None else scale))
-            sc = sc * d if len(sc) == 1 else sc
-            if len(sc) != d:
-                raise ValueError(f"eval_view: scale needs one value or {d}")
-            E = [max(1, int(round((hi - lo) * float(v)))) for (lo, hi), v in zip(win, sc)]
+        axes, batches = self._view_tables("eval_view", window, size, scale)
         tdt, eng, params, lists = self._eval_model("eval_view", dtype, quantized, use_lists, "render_view")
-        axes, batches = [], []
-        for l in range(d):
-            axes.append(blk.view_axis(shape[l], 1, shape[l], win[l][0], win[l][1], E[l])[3])
-            first, nblocks, start, _ = blk.view_axis(n[l], shape[l] // n[l], shape[l], win[l][0], win[l][1], E[l])
-            batches.append((first + np.repeat(np.arange(nblocks), np.diff(start))).astype(np.int32))
-        dev = eng.device
-        res = eng.render_view(params, lists, [torch.from_numpy(a).to(dev) for a in axes],
-                              [torch.from_numpy(b).to(dev) for b in batches], dtype=tdt, want_argmax=want_argmax)
+        axes, batches = ([torch.from_numpy(t).to(eng.device) for t in tabs] for tabs in (axes, batches))
+        res = eng.render_view(params, lists, axes, batches, dtype=tdt, want_argmax=want_argmax)
         return self._eval_result(res, want_argmax, to_host)
 
     def eval_warp(self, matrix, size, **options):
@@ -1418,6 +1432,57 @@ class SharedSmoe(_SmoeBase):
         to the source position ``M (i + 0.5) + t`` in source pixels.  Returns the image ``[*size, C]`` (0 where the view
         leaves the image)."""
         return self.eval_points(blk.warp_points(matrix, size), **options)
+
+    # -- the exact spatial derivative at the same points ----------------------------------------
+    @staticmethod
+    def _grad_result(jac, val, want_values, to_host):
+        if to_host:
+            jac = jac.cpu().numpy()
+            val = None if val is None else val.cpu().numpy()
+        return (jac, val) if want_values else jac
+
+    def eval_points_grad(self, points, quantized=False, want_values=False, to_host=True, use_lists=True):
+        """The model's exact spatial derivative at arbitrary positions, on the device (the engine's ``sample_grad``;
+        include/smoe_hip.h: smoe_shared_sample_grad) -- ``Smoe.sample_grad`` for a whole-image model, which is one continuous
+        function without block seams: an edge map, a structure tensor, the temporal slope of a video model, an alignment
+        step.  Differences of ``eval_points`` sit on the 8-bit lattice; this is the closed-form derivative of the value before
+        the lattice, with the gate mask and the clip held piecewise constant.  ``points``, ``quantized``, ``use_lists`` and
+        the lists are ``eval_points``'s.  Returns ``[..., d, C]`` float32, ``jac[..., l, c] = dv_c / dx_l`` per source pixel
+        (0 outside the image); with ``want_values`` also the float32 values before the lattice ``[..., C]``.
+        ``to_host=False`` returns device tensors.  Several ranks: as ``eval_points``."""
+        _, eng, params, lists = self._eval_model("eval_points_grad", np.float32, quantized, use_lists, "sample_grad")
+        pts, lead = self._eval_points_arg("eval_points_grad", points, eng.device)
+        res = eng.sample_grad(params, lists, pts, want_values=want_values)
+        jac, val = res if want_values else (res, None)
+        jac = jac.reshape(lead + (self.dim_domain, self.channels))
+        val = None if val is None else val.reshape(lead + (self.channels,))
+        return self._grad_result(jac, val, want_values, to_host)
+
+    def eval_view_grad(self, window, size=None, scale=None, quantized=False, want_values=False, to_host=True, use_lists=True):
+        """The derivative on a viewport: ``eval_view``'s ``window`` / ``size`` / ``scale`` and sample positions (the engine's
+        ``render_view_grad``; include/smoe_hip.h: smoe_shared_render_view_grad).  Returns ``[*E, d, C]`` per SOURCE pixel,
+        with ``want_values`` also ``[*E, C]``; the other options are ``eval_points_grad``'s."""
+        axes, batches = self._view_tables("eval_view_grad", window, size, scale)
+        _, eng, params, lists = self._eval_model("eval_view_grad", np.float32, quantized, use_lists, "render_view_grad")
+        axes, batches = ([torch.from_numpy(t).to(eng.device) for t in tabs] for tabs in (axes, batches))
+        res = eng.render_view_grad(params, lists, axes, batches, want_values=want_values)
+        jac, val = res if want_values else (res, None)
+        return self._grad_result(jac, val, want_values, to_host)
+
+    def eval_warp_grad(self, matrix, size, wrt="source", **options):
+        """The derivative of an affine view: ``eval_points_grad`` at the cell centres of ``blocks.warp_points(matrix, size)``,
+        ``[*size, d, C]`` -- ``Smoe.render_warp_grad`` for a whole-image model.  ``wrt="source"``: per source pixel;
+        ``wrt="view"``: per output cell, the chain rule through ``x = M (i + 0.5) + t`` applied on the device,
+        ``J_view[..., m, c] = sum_l J[..., l, c] M[l, m]``.  ``options`` are ``eval_points_grad``'s."""
+        if wrt not in ("source", "view"):
+            raise ValueError('eval_warp_grad: wrt must be "source" or "view"')
+        to_host = options.pop("to_host", True)
+        want_values = options.get("want_values", False)
+        res = self.eval_points_grad(blk.warp_points(matrix, size), to_host=False, **options)
+        jac, val = res if want_values else (res, None)
+        if wrt == "view":
+            jac = _warp_chain(jac, matrix, self.dim_domain)
+        return self._grad_result(jac, val, want_values, to_host)
 
     # hooks of _render
     def _local_rparams(self):
