@@ -164,7 +164,12 @@ int smoe_forward(smoe_handle h, int32_t num_blocks, const float* target, const f
  *                              consecutive calls and they read the same however the iterations are split over calls.
  *                              The entries of such a block are NOT written: arrays passed uninitialised hold garbage there
  *   active    [B] in/out       diverged [B] uint32 in/out (non-zero = block frozen), may be NULL
- *   loss0     [B] iteration-0 loss for the blow-up test, or NULL (NaN test only) */
+ *   loss0     [B] iteration-0 loss for the blow-up test, or NULL (NaN test only)
+ * A tensor that is not trained -- its group's learning rate is 0, train_pis / train_musx / train_gammas is 0 for it, the
+ * slopes only_y_gamma masks, A_corr under radial_as -- is dropped from the optimizer as in the reference (smoe.py:1112-1117):
+ * the variable AND both of its Adam slots leave the call bit for bit as they entered it, in every block and on every tiling
+ * (the slots do not decay towards 0 as they would under a dense step with a zero gradient).  The beta powers and `step`
+ * advance all the same.  smoe_shared_apply / smoe_shared_fit treat an untrained tensor the same way. */
 int smoe_fit(smoe_handle h, int32_t num_blocks, const float* target, const float* loss_w,
              smoe_params* p, smoe_adam_state* s, int32_t n_iters,
              float* loss_last, float* sse_last, uint32_t* active, uint32_t* diverged,

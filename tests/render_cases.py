@@ -10,6 +10,12 @@ from steered_mixture_of_experts_amd import blocks as blk
 from steered_mixture_of_experts_amd.blocks import synthetic_blocks
 
 
+def _lattice(precision=8):
+    """(levels, influence threshold, half-width of the band around it) of a pixel lattice of ``precision`` bits: 255,
+    0.5 / 256 and 1e-6 at 8 bits; the band keeps its share of the threshold (tests/step_parity.influence_threshold)"""
+    return 2 ** precision - 1, 0.5 / 2 ** precision, 1e-6 * 2.0 ** (8 - precision)
+
+
 def _engine(shape, C_, K, **kw):
     from steered_mixture_of_experts_amd.engine import BlockEngine, EngineConfig
     return BlockEngine(EngineConfig(block_shape=shape, channels=C_, kernels=K, **kw))

@@ -1,7 +1,7 @@
 """Teacher-forced step parity of the shared-kernel whole-image fit: ONE Adam step of a ``SharedEngine`` (GPU) or of the
 ``OracleSharedEngine`` test double (CPU) from a state with non-trivial slots and sparse kernel lists, element by element
 against the restatement.  TEST INFRASTRUCTURE, device-agnostic, the shared-mode sibling of tests/step_parity.py (read its
-docstring first: why one step from a prepared state, why the engine's own 8-bit lattice is fed to both restatements).
+docstring first: why one step from a prepared state, why the engine's own pixel lattice is fed to both restatements).
 
 What is different here.  One kernel set serves every batch: a pass leaves one gradient row per batch, the step sums the rows
 of the batches visited since the last step (smoe_shared_accumulate promises exactly that sum) and takes ONE dense Adam step.
@@ -12,7 +12,7 @@ tensor without loosening anything for the rest.
 
 Bounds (tests/step_parity.judge_adam carries the Adam formulas for both modes):
   lattice     the engine's reconstruction against the fp32 restatement's: equal off rounding ties of the quantiser, at most
-              1 LSB on them (test_shared_forward_parity)
+              one level, 1 / (2^precision - 1), on them (step_parity.lattice_check; test_shared_forward_parity's bound)
   loss, sse   per clean batch against the fp64 pass on the engine's lattice: 1e-6 + 2e-5 |ref|
   lists       the new lists of the clean batches equal the fp32 restatement's (with overlap: those of its halo pass); the
               lists of the batches that were not revisited are untouched
@@ -51,7 +51,6 @@ from steered_mixture_of_experts_amd.engine import SharedConfig
 from test_gpu_shared import _bits, _mask, _setup
 
 WARMUP, LATE = sp.WARMUP, sp.LATE
-TAU = 0.5 / 256
 
 # id -> image shape, batch shape, C, kernels per dim, yuv: the smallest shapes that reach
 CASES = {
@@ -69,6 +68,7 @@ _DC = dict(bit_depths=(14, 10, 8, 10, 10), lower_bounds=(-60, -.03, -1, 0, -4), 
 # ``overlap`` is the engine's alone; everything else goes to the engine's and the restatement's configuration alike
 OPTION_LEGS = {
     **sp.OPTION_LEGS,
+    "startpis": dict(pis_l1=0.3, start_pis=50),                 # (the block leg's 9 with a count that is no K of CASES)
     "l1": dict(pis_l1=0.3, u_l1=0.002, lr_steer=1e-2),          # l1clip without the clipping, which leaves the step only the signs
     "radial": dict(radial_as=True),
     "dcq2": dict(diff_center=True, quantization_mode=2, quantize_pis=True, lr_steer=1e-2, **_DC),
@@ -77,6 +77,13 @@ OPTION_LEGS = {
     "ssim": dict(ssim_opt=True),
 }
 _OWN = ("weights", "diff_center", "overlap")
+COAST_TENSORS = ("nu_e", "musX", "A_diagonal")          # the coasting kernel has non-zero slots in each of these that is trained
+
+
+def trained(cfg, name):
+    """Whether the configuration's optimiser moves tensor ``name`` at all (its group's rate, train_*, radial_as)."""
+    return bool(sp._lr(cfg, name) != 0 and {"gamma_e": cfg.train_gammas, "musX": cfg.train_musx, "pis": cfg.train_pis,
+                                            "A_corr": not cfg.radial_as}.get(name, True))
 
 
 @dataclasses.dataclass
@@ -158,7 +165,8 @@ def _build(case, seed, frozen):
         p = o.adam_step(p, f["grads"], st, cfg, np.float32)
     # the coasting kernel: non-zero slots, cleared from every list (of the candidates, the one the fewest batches lose)
     lists = lists.copy()
-    moving = np.all([np.any(st["m"][k][0].reshape(K, -1) != 0, axis=1) for k in ("nu_e", "musX", "A_diagonal")], axis=0)
+    # (of the tensors this configuration trains: the slots of a frozen one stay zero)
+    moving = np.all([np.any(st["m"][k][0].reshape(K, -1) != 0, axis=1) for k in COAST_TENSORS if trained(cfg, k)], axis=0)
     cand = np.flatnonzero(moving & (p["pis"][0] > 0) & lists.any(axis=0))
     assert cand.size, "no kernel with non-zero slots to coast"
     coast = int(cand[np.argmin(lists[:, cand].sum(axis=0))])
@@ -167,11 +175,12 @@ def _build(case, seed, frozen):
     lists[:, absent] = True                 # listed, but prior <= 0: the pass must not train them (nor count them in nact)
     r64 = o.forward(o._bcast(p, NB), tgt, coords, lists, cfg, None if cfg.ssim_opt else lw, np.float64)
     # batches with a gate value on the influence threshold or a blend on the clip edge: discontinuous gradient there
-    tie = (np.abs(r64["w"] - TAU) < 1e-6).any(axis=(1, 2))
+    tau, window = sp.influence_threshold(cfg)
+    tie = (np.abs(r64["w"] - tau) < window).any(axis=(1, 2))
     edge = ((np.abs(r64["y"]) < 1e-6) | (np.abs(r64["y"] - 1) < 1e-6)).any(axis=(1, 2))
     if halo is not None:                    # ... or, for the new list, a gate value of the halo on the threshold
         h64 = o.forward(o._bcast(p, NB), np.zeros(halo.shape[:2] + (C,)), halo.astype(np.float64), lists, cfg, None, np.float64)
-        tie |= (np.abs(h64["w"] - TAU) < 1e-6).any(axis=(1, 2))
+        tie |= (np.abs(h64["w"] - tau) < window).any(axis=(1, 2))
     for d in (p, st["m"], st["v"]):
         for a in d.values():
             a.setflags(write=False)
@@ -303,13 +312,7 @@ def check_shared_step(eng, s):
     q = np.transpose(fw["recon"].cpu().numpy(), (0, 2, 1))
     ref = _ref_pass(s, np.float32, q)
     ref64 = _ref_pass(s, np.float64, q)
-    own = o.fake_quant01(ref["y"], cfg.precision, np.float32)           # the fp32 restatement's lattice
-    levels = 2 ** cfg.precision - 1
-    frac = (np.clip(ref64["y"], 0, 1) * levels + 0.5) % 1.0
-    tie = (frac < 2e-4) | (frac > 1 - 2e-4)
-    d = np.abs(q - own)
-    judge("lattice", d[~tie], 1e-7)
-    judge("lattice_tie", d, 1.0001 / levels)
+    sp.lattice_check(judge, q, ref["y"], ref64["y"], cfg)               # against the fp32 restatement's own lattice
 
     # ---- stale rows: a full pass, dropped ------------------------------------------------------------------------
     eng.accumulate(T, dp, lists.clone())
@@ -357,10 +360,8 @@ def check_shared_step(eng, s):
     k_ = s.coast
     for name in o.PARAM_NAMES:
         lr = sp._lr(cfg, name)
-        trainable = {"gamma_e": cfg.train_gammas, "musX": cfg.train_musx, "pis": cfg.train_pis,
-                     "A_corr": not cfg.radial_as}.get(name, True)
-        if not trainable or lr == 0:
-            count(name + ":moved", int(not (np.array_equal(got[name], s.p[name][0]) and np.array_equal(m1[name], s.m[name][0])
+        if not trained(cfg, name):
+            count("moved:" + name, int(not (np.array_equal(got[name], s.p[name][0]) and np.array_equal(m1[name], s.m[name][0])
                                             and np.array_equal(v1[name], s.v[name][0]))))
             continue
         gb = ref64["grads"][name][c]
@@ -380,7 +381,7 @@ def check_shared_step(eng, s):
         ulp = 2.0 ** -23 * np.maximum(np.abs(x0), 2.0 ** -126)
         should = (m0 != 0) & (np.abs(p_ref[name][0][k_].astype(np.float64) - x0) > 4 * ulp)
         count("coast_still:" + name, (should & (got[name][k_] == x0)).sum())
-        if name in ("nu_e", "musX", "A_diagonal"):
+        if name in COAST_TENSORS:
             count("coast_idle:" + name, int(not should.any()))          # (the scenario itself: something has to move)
     return Result(ratios=ratios, failures=fails, clean=int(c.sum()), batches=NB, runs=len(runs))
 

@@ -9,12 +9,17 @@ chaotic and can only be judged by medians.  A step from a sta
 iterations -- with its slots, beta powers and pruned kernel lists loaded into the engine -- has neither problem: every
 element is compared, and nothing is amplified over iterations.
 
-The 8-bit lattice makes loss and gradients discontinuous at rounding ties, so the engine's OWN lattice (from its evaluation
-pass; a zero-learning-rate fit launch shows that the fit kernel's lattice is the same) is fed to both restatements as
-``q_override``.  The fp64 restatement's own lattice is never used: it differs from an fp32 one in a few pixels per block,
-which alone moves gradients by 6e-4 of their scale.
+The pixel lattice (2^precision - 1 levels) makes loss and gradients discontinuous at rounding ties, so the engine's OWN
+lattice (from its evaluation pass; a zero-learning-rate fit launch shows that the fit kernel's lattice is the same) is fed to
+both restatements as ``q_override``.  The fp64 restatement's own lattice is never used: it differs from an fp32 one in a few
+pixels per block, which alone moves gradients by 6e-4 of their scale.  What is fed to the restatements is itself compared
+with the fp32 restatement's own lattice ("lattice" below): an engine that quantised to another number of levels would
+otherwise agree with the restatement it was handed.
 
-Bounds (all on "clean" blocks: no gate value on the influence threshold, no blend on the clip edge):
+Bounds (all but the lattice on "clean" blocks: no gate value on the influence threshold, no blend on the clip edge):
+  lattice     every pixel of every block: the engine's evaluation-pass reconstruction against the fp32 restatement's own
+              lattice: equal (1e-7) off rounding ties of the quantiser, at most one level, 1 / (2^p - 1), where the fp64 blend
+              times 2^p - 1 sits within 2e-4 of a half-integer (test_forward_parity's bound, generalised from 255 levels)
   loss, sse   rtol 2e-5, the single-pass tolerance of tests/test_gpu_parity.py, against the fp64 pass on the same lattice
   list        equal to the restatement's
   gradients   recovered from the slots, g = (m' - beta1 m) / (1 - beta1):  |g - g64| <= 2e-5 max|g64| per tensor (the bound
@@ -26,6 +31,8 @@ Bounds (all on "clean" blocks: no gate value on the influence threshold, no blen
               0.001 |g| dg / sqrt(v'):
               tol = 1e-6 (|p| + 1) + 2e-5 lr + lr bias [0.1 dg / (sqrt(v') + eps) + |m'| 0.001 |g| dg / (sqrt(v') (sqrt(v') + eps)^2)]
               (test_one_step_parity's tolerance generalised to t > 1)
+  untrained   with lr == 0, radial_as (A_corr) or train_* = False the variable and both of its slots are bit-unchanged, on
+              every block and every tiling (include/smoe_hip.h, smoe_fit)
 """
 import dataclasses
 import functools
@@ -58,7 +65,43 @@ OPTION_LEGS = {
     "ic": dict(train_inverse_cov=True),
     "q2": dict(quantization_mode=2, quantize_pis=True, lr_steer=1e-2, **QKW),
     "q3": dict(quantization_mode=3, quantize_pis=True, lr_steer=1e-2, **QKW),
+    # the switches off their defaults, lr_steer at its default: the normaliser without the determinant factor (and the
+    # su / A_ll term of the diagonal steering gradient gone with it), alone and on the inverse-covariance graph
+    "nodet": dict(use_determinant=False),
+    "nodet_ic": dict(use_determinant=False, train_inverse_cov=True),
+    # one frozen tensor each; train_gammas=False also takes the slopes out of the forward graph
+    "fz_pis": dict(train_pis=False),
+    "fz_mus": dict(train_musx=False),
+    "fz_gam": dict(train_gammas=False),
+    # the lattice, the influence threshold and the margin follow the precision
+    "p10": dict(precision=10),
+    "p6": dict(precision=6),
+    # 0.25: eps = margin / 2^p must stay clear of the lattice step 1 / (2^p - 1).  At margin 1.0 (1/256 against 1/255) pixels
+    # one level off contribute a cancelled residue |d| - eps and the fp32 restatement alone uses 0.19 of the gradient
+    # tolerance, at 1.5 more than half of it; at 0.25 it stays below 0.07
+    "margin": dict(margin=0.25),
+    # a normaliser of the l1 term that is no kernel count in use (4, 8, 36, 32, 272)
+    "startpis": dict(pis_l1=0.3, start_pis=9),
 }
+
+
+def influence_threshold(cfg):
+    """(tau, window): the influence threshold 0.5 / 2^precision of the gate and the half-width of the band around it in which a
+    gate value makes its block's gradient discontinuous.  The band scales with the threshold, 1e-6 * 2^(8 - precision): 0.05 %
+    of tau at every precision, and 0.5 / 256 with 1e-6 exactly at 8 bits."""
+    return 0.5 / 2 ** cfg.precision, 1e-6 * 2.0 ** (8 - cfg.precision)
+
+
+def lattice_check(judge, q, y32, y64, cfg):
+    """The "lattice" comparison of the module docstring, shared with tests/shared_step_parity.py.  ``q``: the engine's
+    reconstruction; ``y32`` / ``y64``: the blends of the fp32 / fp64 restatement."""
+    own = o.fake_quant01(y32, cfg.precision, np.float32)
+    levels = 2 ** cfg.precision - 1
+    frac = (np.clip(y64, 0, 1) * levels + 0.5) % 1.0
+    tie = (frac < 2e-4) | (frac > 1 - 2e-4)
+    d = np.abs(q - own)
+    judge("lattice", d[~tie], 1e-7)
+    judge("lattice_tie", d, 1.0001 / levels)
 
 
 def blocks_for(shape):
@@ -155,7 +198,8 @@ def _build_one(shape, C, kpd, yuv, B, seed, opts, kind, corner):
         flag_matters = bool(a_m[corner, 0] and not a_s[corner, 0])
     r64 = o.forward(p, tgt, coords, active, cfg, None if cfg.ssim_opt else lw, np.float64, fed=fed)
     # blocks with a gate value on the influence threshold or a blend on the clip edge: discontinuous gradient there
-    tie = (np.abs(r64["w"] - 0.5 / 256) < 1e-6).any(axis=(1, 2))
+    tau, window = influence_threshold(cfg)
+    tie = (np.abs(r64["w"] - tau) < window).any(axis=(1, 2))
     edge = ((np.abs(r64["y"]) < 1e-6) | (np.abs(r64["y"] - 1) < 1e-6)).any(axis=(1, 2))
     for d in (p, st["m"], st["v"]):
         for a in d.values():
@@ -268,6 +312,7 @@ def check_step(eng, s, eng0=None):
     fw_loss, fw_sse = fw["loss"].cpu().numpy(), fw["sse"].cpu().numpy()
     ref = _ref_pass(s.p, s, np.float32, q)
     ref64 = _ref_pass(s.p, s, np.float64, q)
+    lattice_check(judge, q, ref["y"], ref64["y"], cfg)
     clean = s.clean
     dropped = 0
     if eng0 is not None:
@@ -289,7 +334,10 @@ def check_step(eng, s, eng0=None):
         s0 = torch.zeros(B, device=eng0.device)
         eng0.fit(T, dp0, st0, act0, 1, loss_w=LW, loss_out=l0, sse_out=s0, loss_w_is_sample=sample)
         for k, v in _host(dp0).items():
-            assert np.array_equal(v, s.p[k].astype(np.float32)), k          # zero learning rates: nothing moved
+            assert np.array_equal(v, s.p[k].astype(np.float32)), k          # zero learning rates: nothing moved,
+        for k in o.PARAM_NAMES:                                             # the slots neither
+            assert np.array_equal(st0.m[k].cpu().numpy(), s.m[k].astype(np.float32)), ("m", k)
+            assert np.array_equal(st0.v[k].cpu().numpy(), s.v[k].astype(np.float32)), ("v", k)
         rt = max(2e-6, 4.0 * np.sqrt(s.tgt.shape[1] * s.tgt.shape[2]) * 2.0 ** -24)
         e_s, t_s = np.abs(s0.cpu().numpy() - fw_sse), 1e-9 + rt * np.abs(fw_sse)
         e_l, t_l = np.abs(l0.cpu().numpy() - fw_loss), 1e-12 + rt * np.abs(fw_loss)
@@ -331,8 +379,12 @@ def check_step(eng, s, eng0=None):
         trainable = {"gamma_e": cfg.train_gammas, "musX": cfg.train_musx, "pis": cfg.train_pis,
                      "A_corr": not cfg.radial_as}.get(name, True)
         if not trainable or lr == 0:
-            if not np.array_equal(got[name], s.p[name]):
-                fails.append((name + ":moved", 0))
+            # (every block, clean or not: the variable and both slots bit-unchanged)
+            moved = [w for w, a, a0 in (("p", got[name], s.p[name]), ("m", m1[name], s.m[name]), ("v", v1[name], s.v[name]))
+                     if not np.array_equal(a, a0.astype(np.float32))]
+            ratios["moved:" + name] = float(len(moved))
+            if moved:
+                fails.append(("moved:" + name, "/".join(moved)))
             continue
         g64 = ref64["grads"][name][c]
         # (with grad_clip the kernel clips a gradient whose rounding error is that of the UNCLIPPED tensor: its scale, as in
@@ -353,4 +405,4 @@ def worst(ratios):
 
 
 __all__ = ["SHAPES", "KINDS", "OPTION_LEGS", "QKW", "build_state", "check_step", "engine_kwargs", "judge_adam", "load_state", "worst",
-           "blocks_for", "WARMUP", "LATE"]
+           "blocks_for", "influence_threshold", "lattice_check", "WARMUP", "LATE"]

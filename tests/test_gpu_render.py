@@ -13,7 +13,7 @@ import pytest
 import torch
 
 from oracle import smoe_oracle as o
-from render_cases import _axes, _bits, _dev_axes, _engine, _guarded, _image, _owned, _setup, _to_dev
+from render_cases import _axes, _bits, _dev_axes, _engine, _guarded, _image, _lattice, _owned, _setup, _to_dev
 from render_engine import oracle_blocks, place_blocks
 from steered_mixture_of_experts_amd import blocks as blk
 from steered_mixture_of_experts_amd.blocks import synthetic_blocks
@@ -120,11 +120,18 @@ RESAMPLED = [
     ((12, 10, 3), 3, [2, 2, 1], True, (6, 5, 9), {}),
     ((16, 16), 3, [2, 2], True, (40, 24), dict(train_inverse_cov=True)),
     ((7, 5), 1, [2, 2], False, (3, 300), {}),    # 300 > 256 innermost samples: CL = 256, two passes, the second ragged
+    # off the 8-bit lattice (nudged_max, inv_scale and the influence threshold follow the precision): 1 023 and 63 levels
+    ((16, 16), 3, [2, 2], True, (40, 24), dict(precision=10)),
+    ((16, 16), 3, [2, 2], True, (40, 24), dict(precision=6)),
 ]
 
 
+def _tag(kw):
+    return "".join("-ic" if k == "train_inverse_cov" else f"-p{v}" for k, v in kw.items())
+
+
 @pytest.mark.parametrize("case", RESAMPLED, ids=["x".join(map(str, c[0])) + "-c%d-to-" % c[1] + "x".join(map(str, c[4]))
-                                                 + ("-ic" if c[5] else "") for c in RESAMPLED])
+                                                 + _tag(c[5]) for c in RESAMPLED])
 def test_parity_on_resampled_grids(case):
     shape, C_, kpd, yuv, m, kw = case
     cfg, p, tgt, K, active = _parity_inputs(shape, C_, kpd, yuv, **kw)
@@ -134,14 +141,14 @@ def test_parity_on_resampled_grids(case):
     tabs = _axes(shape, m)
     ref, _ = oracle_blocks(p, active, tabs, cfg, np.float32)
     ref64, _ = oracle_blocks(p, active, tabs, cfg, np.float64)
-    lsb = 1.0 / 255
-    frac = (np.clip(ref64["y"], 0, 1) * 255 + 0.5) % 1.0
+    levels, tau, band = _lattice(cfg.precision)
+    lsb = 1.0 / levels
+    frac = (np.clip(ref64["y"], 0, 1) * levels + 0.5) % 1.0
     tie = (frac < 2e-4) | (frac > 1 - 2e-4)
-    tau = 0.5 / 256
-    near_tau = (np.abs(ref64["w"] - tau) < 1e-6).any(axis=1)[..., None]                 # (B, M, 1)
+    near_tau = (np.abs(ref64["w"] - tau) < band).any(axis=1)[..., None]                 # (B, M, 1)
     loose = tie | near_tau
     # condition on the inputs: the restatement itself has few ties and no fp32-vs-fp64 difference outside them
-    print(f"oracle: tie share {tie.mean():.2e}, near-threshold gate entries {(np.abs(ref64['w'] - tau) < 1e-6).mean():.2e}, "
+    print(f"oracle: tie share {tie.mean():.2e}, near-threshold gate entries {(np.abs(ref64['w'] - tau) < band).mean():.2e}, "
           f"loose share {loose.mean():.2e}")
     assert loose.mean() < 0.01
     assert (np.abs(ref["recon"] - ref64["recon"])[~np.broadcast_to(loose, tie.shape)] < 1e-7).all()
@@ -153,9 +160,9 @@ def test_parity_on_resampled_grids(case):
     extent = [g * mm for g, mm in zip(grid, m)]
     axes = _dev_axes(tabs)
     img = eng.render(dp, act, axes, grid, extent)
-    u8 = eng.render(dp, act, axes, grid, extent, dtype=torch.uint8)
+    u8 = eng.render(dp, act, axes, grid, extent, dtype=torch.uint8) if cfg.precision <= 8 else None     # (refused above 8 bits)
     torch.cuda.synchronize()
-    img, u8 = img.cpu().numpy(), u8.cpu().numpy()
+    img = img.cpu().numpy()
     own = _owned(m, grid, extent, 0, B37)
     want = place_blocks(ref["recon"].astype(np.float32), m, grid, extent, 0, np.zeros(tuple(extent) + (C_,), np.float32))
     loose_img = place_blocks(np.broadcast_to(loose, tie.shape), m, grid, extent, 0, np.zeros(tuple(extent) + (C_,), bool))
@@ -166,7 +173,9 @@ def test_parity_on_resampled_grids(case):
     assert (dd[~lo] < 1e-7).all(), dd[~lo].max()
     assert (dd <= lsb * 1.0001).all(), dd.max()
     # 6. uint8 = the lattice index of the fp32 image
-    assert np.array_equal(u8, np.rint(img * 255).astype(np.uint8))
+    if u8 is not None:
+        assert np.array_equal(u8.cpu().numpy(), np.rint(img * levels).astype(np.uint8))
+    assert np.abs(img * levels - np.rint(img * levels)).max() < 1e-3                   # on the lattice of this precision
     eng.close()
 
 

@@ -23,7 +23,11 @@ STEP_CASES = [(c, False, None) for c in ("A", "B", "C", "C3", "D")] + [("A", Tru
 STEP_CASES += [("A", False, "l1clip"), ("A", False, "l1")]
 STEP_CASES += [("B", False, leg) for leg in ("qpis", "q2", "q3", "ic", "radial", "dcq2", "lw", "ov3")]
 STEP_CASES += [("S", False, "ssim"), ("C", False, "q3")]
-PATH_CASES = [("A", None), ("B", None), ("C", None), ("D", None), ("B", "q3"), ("S", "ssim")]
+# the switches off their defaults; the determinant and the precision on the 3-d code as well
+NEW_LEGS = ("nodet", "nodet_ic", "fz_pis", "fz_mus", "fz_gam", "p10", "p6", "margin", "startpis")
+STEP_CASES += [("B", False, leg) for leg in NEW_LEGS] + [("D", False, "nodet"), ("D", False, "p10")]
+# (smoe_shared_fit fills its kernel arguments -- use_det, reg_pi, the precision's constants -- apart from accumulate / apply)
+PATH_CASES = [("A", None), ("B", None), ("C", None), ("D", None), ("B", "q3"), ("S", "ssim"), ("B", "p10"), ("B", "nodet")]
 
 
 def state_of(cid, late, leg):

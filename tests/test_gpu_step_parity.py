@@ -3,7 +3,9 @@
 (a) ONE Adam step from a state with non-trivial slots, beta powers and a partial kernel list, element by element against
     the restatement: every shape of test_gpu_parity.SHAPES x every fit tiling x loss-weight kinds (padding mask, fractional,
     pixel sub-sample, none) x two states (t = 7, beta powers of step 150), the option legs (l1 + clip, quantize_pis,
-    train_inverse_cov, quantization_mode 2 / 3) with a padding mask, and the SSIM graph with weights passed.
+    train_inverse_cov, quantization_mode 2 / 3; the switches off their defaults: use_determinant, each train_*, precision
+    6 / 10, margin, start_pis) with a padding mask, precision 10 and use_determinant=False without weights too (the
+    unweighted kernels are instantiations of their own), and the SSIM graph with weights passed.
 (b) Six iterations as one launch of 6, as 2 + 4 and as 6 x 1 give bit-identical parameters, slots, lists, flags and losses:
     inside a launch the kernel advances the beta powers and refreshes its derived LDS state itself, at a launch boundary
     it rebuilds them from global memory and from the host's running products.
@@ -31,8 +33,10 @@ KIND_STATES = [("pad", False), ("frac", False), ("sample", False), ("none", True
 LEG_SHAPES = [SHAPES[1], SHAPES[2], SHAPES[3]]          # (16,16)/3, (32,32)/3, (16,16,4)/3
 # train_inverse_cov has its own instantiation on the 16-, 32- and 64-lane tilings (the basic set), quantization_mode 2 / 3
 # and SSIM on the 16- and 64-lane tilings only; the pair, duo and team tilings carry the plain margin-loss graph
-LEG_TILINGS = {"l1clip": (16, 64, 32, 128, 264, 816), "qpis": (16, 64, 32, 128, 264, 816), "ic": (16, 64, 32), "q2": (16, 64),
-               "q3": (16, 64)}
+_ALL, _BASIC = (16, 64, 32, 128, 264, 816), (16, 64, 32)
+LEG_TILINGS = {"l1clip": _ALL, "qpis": _ALL, "ic": _BASIC, "q2": (16, 64), "q3": (16, 64),
+               "nodet": _ALL, "nodet_ic": _BASIC, "fz_pis": _ALL, "fz_mus": _ALL, "fz_gam": _ALL, "p10": _ALL, "p6": _ALL, "margin": _ALL,
+               "startpis": _ALL}
 # ... and blocks of 1 024 pixels with loss weights do not fit the 16-lane quantised kernels' LDS (four blocks per wavefront,
 # each with its pixel rows, its weights and the quantised parameter image): the library refuses them, see
 # test_weighted_big_blocks_are_refused_by_the_16_lane_quantised_kernels
@@ -42,6 +46,8 @@ NO_G16_QUANT = lambda s, t, leg: leg in ("q2", "q3") and t == 16 and int(np.prod
 STEP_CASES = [(s, t, kind, late, None) for s, t in TILINGS for kind, late in KIND_STATES]
 STEP_CASES += [(s, t, "pad", False, leg) for leg in sp.OPTION_LEGS for s in LEG_SHAPES for t in LEG_TILINGS[leg]
                if (s, t) in TILINGS and not NO_G16_QUANT(s, t, leg)]
+# without weights the kernels accumulate the raw margin loss, (|diff| - eps)^2 per channel, in instantiations of their own
+STEP_CASES += [(s, t, "none", True, leg) for leg in ("p10", "nodet") for s in LEG_SHAPES for t in (16, 64)]
 
 
 def _name(s):
@@ -71,7 +77,7 @@ def expect_variant(name, tiling, N, weighted, graph=None, sample=False, unweight
         assert (("+" + g) in name) == (g == graph), name
 
 
-_GRAPH = {"ic": "ic", "q2": "quant", "q3": "quant"}
+_GRAPH = {"ic": "ic", "nodet_ic": "ic", "q2": "quant", "q3": "quant"}
 WORST = {}
 
 

@@ -124,6 +124,43 @@ def test_render_evaluates_the_model_at_pixel_centres():
     assert abs(out[0, 0, 0] - (nu + (g0 + g1) * u[0])) < 1 / 255
 
 
+@pytest.mark.parametrize("precision", [6, 10])
+def test_restatement_renders_on_the_lattice_of_the_precision(precision):
+    """The CPU half of test_gpu_render.py's precision cases: the same model and sample tables through the restatement and
+    the stand-in engine.  The image sits on the lattice of 2^p - 1 levels (at 10 bits NOT on the 255-level one), the 8-bit
+    image is the lattice index, and the condition on the inputs that the GPU case asserts holds."""
+    import torch
+    from render_cases import _axes, _lattice, _setup
+    from render_engine import oracle_blocks
+    from steered_mixture_of_experts_amd.engine import EngineConfig
+    shape, C_, kpd, m, B = (16, 16), 3, [2, 2], (40, 24), 37
+    cfg, p, _, K = _setup(shape, C_, kpd, True, B, 100 + len(shape) + C_, precision=precision)
+    active = np.random.default_rng(5).uniform(size=(B, K)) < 0.85
+    levels, tau, band = _lattice(precision)
+    assert (levels, tau) == (2 ** precision - 1, 0.5 / 2 ** precision) and _lattice(8) == (255, 0.5 / 256, 1e-6)
+    tabs = _axes(shape, m)
+    ref, _ = oracle_blocks(p, active, tabs, cfg, np.float32)
+    ref64, _ = oracle_blocks(p, active, tabs, cfg, np.float64)
+    frac = (np.clip(ref64["y"], 0, 1) * levels + 0.5) % 1.0
+    loose = ((frac < 2e-4) | (frac > 1 - 2e-4)) | (np.abs(ref64["w"] - tau) < band).any(axis=1)[..., None]
+    assert loose.mean() < 0.01
+    assert (np.abs(ref["recon"] - ref64["recon"])[~np.broadcast_to(loose, frac.shape)] < 1e-7).all()
+    idx = ref["recon"].astype(np.float64) * levels
+    assert np.abs(idx - np.rint(idx)).max() < 1e-3 and np.rint(idx).max() <= levels and len(np.unique(np.rint(idx))) > levels // 4
+    if precision > 8:
+        assert np.abs(ref["recon"] * 255 - np.rint(ref["recon"] * 255)).max() > 0.25
+    eng = OracleRenderEngine(EngineConfig(block_shape=shape, channels=C_, kernels=K, use_yuv=True, precision=precision))
+    dp = {k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)) for k, v in p.items()}
+    bits = torch.from_numpy((active.astype(np.uint32) << np.arange(K, dtype=np.uint32)[None, :]).sum(axis=1).astype(np.uint32).view(np.int32))
+    grid, axes = (5, 8), [torch.from_numpy(np.ascontiguousarray(t)) for t in tabs]
+    extent = [g * mm for g, mm in zip(grid, m)]
+    img = eng.render(dp, bits, axes, grid, extent).numpy()
+    assert np.array_equal(img[:m[0], :m[1]].reshape(-1, C_), ref["recon"][0].astype(np.float32))
+    if precision <= 8:
+        u8 = eng.render(dp, bits, axes, grid, extent, dtype=torch.uint8).numpy()
+        assert np.array_equal(u8, np.rint(img * levels).astype(np.uint8)) and u8.max() <= levels
+
+
 def test_quantized_render_is_the_qreconstruction():
     img = _image(32, 32, seed=2)
     s = _make(img, quantization_mode=1)

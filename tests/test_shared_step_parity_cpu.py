@@ -6,8 +6,10 @@ import numpy as np
 import pytest
 
 import shared_step_parity as ssp
+import step_parity as sp
 import test_gpu_shared_step_parity as g
 from fake_engine import OracleSharedEngine
+from oracle import smoe_oracle as o
 
 
 def _engine(s, cls=OracleSharedEngine, *args):
@@ -119,8 +121,81 @@ class KernelsPast255Skipped(OracleSharedEngine):
         return super().accumulate(target, params, lists, first_batch, **kw)
 
 
+# ---- one mutant per switch of the new option legs: the engine ignores what it was configured with ------------------
+class DeterminantKept(OracleSharedEngine):
+    """use_determinant=False ignored."""
+
+    def __init__(self, cfg, device=None):
+        super().__init__(cfg, device)
+        assert not self.ocfg.use_determinant
+        self.ocfg.use_determinant = True
+
+
+class FrozenTensorTrained(OracleSharedEngine):
+    """train_pis / train_musx = False ignored in the step: the tensor's rate is not zeroed."""
+
+    def apply(self, params, state):
+        assert not (self.ocfg.train_pis and self.ocfg.train_musx)
+        keep = self.ocfg
+        self.ocfg = o.OracleConfig(**{**keep.__dict__, "train_pis": True, "train_musx": True})
+        try:
+            return super().apply(params, state)
+        finally:
+            self.ocfg = keep
+
+
+class FrozenSlotsAdvance(FrozenTensorTrained):
+    """the frozen tensor stays where it is, but its slots take the step."""
+
+    def apply(self, params, state):
+        keep = {k: params[k].clone() for k in ("pis", "musX")}
+        super().apply(params, state)
+        for k, on in (("pis", self.ocfg.train_pis), ("musX", self.ocfg.train_musx)):
+            if not on:
+                params[k].copy_(keep[k])
+
+
+class GammasKept(OracleSharedEngine):
+    """train_gammas=False ignored: the slopes stay in the forward graph and are trained."""
+
+    def __init__(self, cfg, device=None):
+        super().__init__(cfg, device)
+        assert not self.ocfg.train_gammas
+        self.ocfg.train_gammas = True
+
+
+class Levels255(OracleSharedEngine):
+    """the pixel lattice has 255 levels whatever the precision; threshold and margin follow it.  Only the lattice comparison
+    can see it: everything else belongs to the lattice the checker feeds to the restatements."""
+
+    def _on_255(self, call, *a, **kw):
+        assert self.ocfg.precision != 8
+        real = o.fake_quant01
+        o.fake_quant01 = lambda y, precision, T: real(y, 8, T)
+        try:
+            return call(*a, **kw)
+        finally:
+            o.fake_quant01 = real
+
+    def forward(self, *a, **kw):
+        return self._on_255(super().forward, *a, **kw)
+
+    def accumulate(self, *a, **kw):
+        return self._on_255(super().accumulate, *a, **kw)
+
+
+class KernelsForStartPis(OracleSharedEngine):
+    """the l1 term of the priors normalised by the kernel count, start_pis ignored."""
+
+    def __init__(self, cfg, device=None):
+        super().__init__(cfg, device)
+        assert self.ocfg.start_pis not in (None, cfg.kernels) and self.ocfg.pis_l1 > 0
+        self.ocfg.start_pis = cfg.kernels
+
+
 # ------------------------------------------------------------------------------------------------------------------
 ACCEPT = [("B", False, None), ("C", False, None), ("B", True, "q3"), ("A", False, "l1clip"), ("A", False, "l1")]
+ACCEPT += [("B", False, leg) for leg in g.NEW_LEGS] + [("D", False, "nodet"), ("D", False, "p10")]
 
 
 @pytest.mark.parametrize("case", ACCEPT, ids=[g._id(c) for c in ACCEPT])
@@ -168,7 +243,7 @@ def test_every_gpu_matrix_state_meets_the_precondition():
         assert np.any(s.m["nu_e"][0, s.coast] != 0)
         assert trained.sum(0).max() < batches                      # nact < NB: the l1 terms can tell them apart
         assert len(ssp._runs(s.clean)) >= 2 or clean == batches    # (several accumulate calls, unless nothing is excluded)
-    assert len(seen) == 17
+    assert len(seen) == 17 + len(g.NEW_LEGS) + 2
     # the shapes reach what they are there for
     a, b, c = (g.state_of(x, False, None) for x in "ABC")
     assert a.NB == 289 and a.clean[256:].any() and a.clean[-1] and b.NB == 90 and b.clean[64:].any()
@@ -203,6 +278,55 @@ def test_checker_rejects_the_mutant(mutant, cid, late, leg):
         # (it leaves every kernel that no batch trained, the two with a prior <= 0 included: the comparisons of the whole tensor
         # see those as well)
         assert {"coast_grad", "coast_m", "coast_v2", "coast_param", "coast_still"} <= kinds, res.failures
+
+
+SWITCH_MUTANTS = [
+    # mutant, case id, leg, the comparisons that may (and at least one of which must) see it
+    (DeterminantKept, "B", "nodet", None), (DeterminantKept, "D", "nodet", None), (DeterminantKept, "B", "nodet_ic", None),
+    (FrozenTensorTrained, "B", "fz_pis", {"moved"}), (FrozenTensorTrained, "B", "fz_mus", {"moved"}),
+    (FrozenSlotsAdvance, "B", "fz_pis", {"moved"}), (FrozenSlotsAdvance, "B", "fz_mus", {"moved"}),
+    (GammasKept, "B", "fz_gam", None),
+    (Levels255, "B", "p10", {"lattice", "lattice_tie"}), (Levels255, "D", "p10", {"lattice", "lattice_tie"}),
+    (Levels255, "B", "p6", {"lattice", "lattice_tie"}),
+    (KernelsForStartPis, "B", "startpis", {"loss", "grad", "v", "param"}),
+]
+
+
+@pytest.mark.parametrize("mutant,cid,leg,seen_by", SWITCH_MUTANTS, ids=[f"{m.__name__}-{c}-{leg}" for m, c, leg, _ in SWITCH_MUTANTS])
+def test_checker_rejects_an_engine_that_ignores_the_switch(mutant, cid, leg, seen_by):
+    s = g.state_of(cid, False, leg)
+    res = ssp.check_shared_step(_engine(s, mutant), s)
+    print(mutant.__name__, cid, leg, res.failures[:6])
+    assert res.failures, res.ratios
+    if seen_by is not None:
+        assert {n.split(":")[0] for n, _ in res.failures} <= seen_by, res.failures
+
+
+def test_precision_8_masks_are_the_ones_of_the_fixed_threshold():
+    """The influence threshold and its band follow cfg.precision (step_parity.influence_threshold); at 8 bits the clean masks
+    of the GPU matrix's states are those of the constants they were built with before, 0.5 / 256 and 1e-6, bit for bit."""
+    n = 0
+    for cid, leg in [("A", None), ("B", None), ("C", None), ("D", None), ("A", "l1clip"), ("B", "ov3"), ("B", "lw"), ("B", "nodet")]:
+        s = g.state_of(cid, False, leg)
+        assert s.cfg.precision == 8 and sp.influence_threshold(s.cfg) == (0.5 / 256, 1e-6)
+        r64 = o.forward(o._bcast(s.p, s.NB), s.tgt, s.coords, s.lists, s.cfg, s.lw, np.float64)
+        tie = (np.abs(r64["w"] - 0.5 / 256) < 1e-6).any(axis=(1, 2))
+        edge = ((np.abs(r64["y"]) < 1e-6) | (np.abs(r64["y"] - 1) < 1e-6)).any(axis=(1, 2))
+        if s.halo is not None:
+            h64 = o.forward(o._bcast(s.p, s.NB), np.zeros(s.halo.shape[:2] + (s.tgt.shape[2],)), s.halo.astype(np.float64), s.lists,
+                            s.cfg, None, np.float64)
+            tie |= (np.abs(h64["w"] - 0.5 / 256) < 1e-6).any(axis=(1, 2))
+        assert np.array_equal(s.clean, ~(tie | edge)), (cid, leg)
+        n += 1
+    assert n == 8
+
+
+def test_coasting_kernel_is_picked_among_the_trained_tensors():
+    """With train_musx=False the musX slots stay zero: the picker looks at the tensors the configuration trains."""
+    s = g.state_of("B", False, "fz_mus")
+    assert not s.m["musX"].any() and not s.v["musX"].any()
+    assert np.any(s.m["nu_e"][0, s.coast] != 0) and np.any(s.m["A_diagonal"][0, s.coast] != 0)
+    assert ssp.trained(s.cfg, "nu_e") and not ssp.trained(s.cfg, "musX")
 
 
 def test_checker_rejects_a_cleared_list_bit_treated_as_set():
