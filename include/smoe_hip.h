@@ -357,6 +357,49 @@ int smoe_sample_grad(smoe_handle h, const smoe_params* p, const uint32_t* active
                      const int32_t length[3], const float* points, int64_t num_points, const float blend[3],
                      float* jac, float* values, int32_t* block, void* stream);
 
+/* Anti-aliased point decode: per output sample the mean of the model over a small regular grid of taps inside the sample's
+ * footprint in the source image -- a thumbnail with fewer samples than pixels, a zoomed-out warp, a stabilised video view.
+ * smoe_sample takes one position per sample, so a decode coarser than the source aliases; this one integrates over the cell.
+ *   points, grid, length, p, active, blend     smoe_sample's; a point is the CENTRE of an output cell
+ *   footprint                HOST [dim, dim] fp32, row-major, source pixels: column m is the edge vector of an output cell along
+ *                            view axis m (an affine view x = M i + t: footprint = M).  One footprint serves all points of a call
+ *   taps                     HOST [dim] int32, 1 <= taps[m] <= 16, prod(taps) <= 64: the taps along view axis m
+ *   values                   [num_points, C] or NULL, SMOE_IMAGE_F32 (lattice values) or SMOE_IMAGE_U8 (lattice indices): the mean
+ *                            put on the lattice by the rounding smoe_sample applies to its own results, floor(v (2^p - 1) + 1/2)
+ *   mean                     [num_points, C] fp32 or NULL: the mean before the lattice
+ *   count                    [num_points] uint8 or NULL: the taps inside the image
+ *   block                    [num_points] or NULL: int32 image-wide index of the own block of the centre, -1 = centre outside (a
+ *                            centre outside with taps inside still gets their mean)
+ * Per point x and tap multi-index j (0 <= j_m < taps[m]), all in IEEE fp32:
+ *   tap offset               o_m = (float)(2 j_m + 1 - taps[m]) / (float)(2 taps[m]): an exact integer numerator, one correctly
+ *                            rounded division
+ *   tap position             t_l = x_l, then for m = 0 .. dim-1: t_l = t_l + (F[l][m] * o_m), product and sum rounded separately
+ *                            (never fused), so numpy float32 gives the position bit for bit (blocks.area_taps).  With
+ *                            taps[m] == 1 the offset is 0 and the tap is the point itself
+ *   tap value                the tap is resolved exactly as a point of smoe_sample_grad -- the same outside rule against length,
+ *                            own block g and block-unit coordinate u, with blend the same cross-fade -- and its value is that
+ *                            call's `values` V (before the lattice), bit for bit
+ *   mean                     acc_c = 0, cnt = 0; over the taps in row-major order of j (last axis fastest) an inside tap adds
+ *                            acc_c = acc_c + V_c (one fp32 add) and cnt += 1; mean_c = acc_c / (float)cnt, correctly rounded;
+ *                            cnt == 0 gives 0.  Taps outside the image are left out, not counted as black: an edge cell of a
+ *                            thumbnail stays as bright as its inside
+ * No argmax: an average has no single kernel.  The result for a point depends on its coordinates, footprint, taps and the
+ * model only: not on num_points, its place in the list, the other points, staging or how the launch is cut.
+ * Limits: one footprint per call (an affine view); at most 64 taps (an 8 x 8 box: a 1/8 thumbnail; 4 x 4 x 4: video);
+ * per-block models only -- there is no counterpart for the whole-image models of smoe_shared_sample.
+ * A workgroup takes 256 consecutive points and bounds the blocks of all their taps: the centres' box widened per axis by the
+ * footprint's half extent 0.5 sum_m |F[l][m]| plus one block (with blend: one more); records are staged as in smoe_sample where
+ * that box fits the budget (SMOE_SAMPLE_RECORDS applies), and both paths give the same bits.  Offsets are 64-bit; stores are 16
+ * bytes wide where values / mean / count / block are 16-byte aligned, element-wise at ragged heads and tails.
+ * num_points == 0 is a successful no-op.  SMOE_ERR_INVALID names the offending argument: smoe_sample's cases (values excepted),
+ * a null footprint / taps, a non-finite footprint entry, taps[m] outside 1 .. 16, prod(taps) > 64, (num_points > 0) values and
+ * mean both NULL.  SMOE_ERR_UNSUPPORTED: grid[l] * block_shape[l] > 2^24, SMOE_IMAGE_U8 values with precision > 8, 2^31 or more
+ * workgroups, more than 160 KB of LDS. */
+int smoe_sample_area(smoe_handle h, const smoe_params* p, const uint32_t* active, const int32_t grid[3],
+                     const int32_t length[3], const float* points, int64_t num_points, const float* footprint,
+                     const int32_t* taps, const float blend[3], void* values, int32_t image_format, float* mean,
+                     uint8_t* count, int32_t* block, void* stream);
+
 /* Name of the kernel variant smoe_fit would launch for num_blocks (diagnostics / profiles). */
 const char* smoe_fit_variant(smoe_handle h, int32_t num_blocks);
 

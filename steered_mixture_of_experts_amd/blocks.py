@@ -149,6 +149,17 @@ def view_axis(n: int, grid_l: int, length_l, lo, hi, E: int):
     return first, blocks, start, coords
 
 
+def view_positions(lo, hi, E: int) -> np.ndarray:
+    """The sample positions of one axis of a viewport in source pixels, as ``view_axis`` places them: ``x_i = lo + (i + 0.5)
+    (hi - lo) / E``, computed exactly (``lo`` and ``hi`` are taken as the float64 they are) and rounded to float32 once.
+    Returns float32 ``[E]`` -- the cell centres ``Smoe.render_view(taps=...)`` hands to ``sample_area``."""
+    E = int(E)
+    if E < 1:
+        raise ValueError("view_positions: E must be >= 1")
+    flo, half = Fraction(float(lo)), (Fraction(float(hi)) - Fraction(float(lo))) / (2 * E)
+    return np.array([_round_once_f32(flo + (2 * i + 1) * half) for i in range(E)], dtype=np.float32)
+
+
 def point_blocks(points, block_shape: Sequence[int], grid: Sequence[int], length: Sequence[int]):
     """Where arbitrary positions fall (``Smoe.sample``, include/smoe_hip.h: smoe_sample) -- the one host statement of the
     mapping, in float32 throughout, as the kernel computes it.  ``points`` ``[..., d]`` in source pixels, axis order of the
@@ -197,6 +208,60 @@ def warp_points(matrix, size: Sequence[int]) -> np.ndarray:
         raise ValueError("warp_points: size needs entries >= 1")
     idx = np.stack(np.meshgrid(*[np.arange(e, dtype=np.float64) + 0.5 for e in size], indexing="ij"), axis=-1)
     return (idx @ A[:, :d].T + A[:, d]).astype(np.float32)
+
+
+AREA_AXIS_TAPS = 16     # taps per view axis of an area-averaged sample, at most (include/smoe_hip.h: smoe_sample_area)
+AREA_TAPS = 64          # taps per sample, at most
+
+
+def area_args(footprint, taps, d: int):
+    """``footprint`` as float32 ``[d, d]`` and ``taps`` as ``d`` ints, checked as smoe_sample_area checks them."""
+    F = np.asarray(footprint, dtype=np.float32)
+    if F.shape != (d, d) or not np.isfinite(F).all():
+        raise ValueError(f"footprint must be a finite [{d}, {d}] array")
+    tp = [int(v) for v in np.atleast_1d(taps)]
+    tp = tp * d if len(tp) == 1 else tp
+    if len(tp) != d or min(tp) < 1 or max(tp) > AREA_AXIS_TAPS:
+        raise ValueError(f"taps needs one value or {d}, each 1 .. {AREA_AXIS_TAPS}")
+    if int(np.prod(tp)) > AREA_TAPS:
+        raise ValueError(f"taps must not multiply to more than {AREA_TAPS}")
+    return F, tp
+
+
+def area_taps(points, footprint, taps) -> np.ndarray:
+    """The tap positions of area-averaged samples (``Smoe.sample_area``, include/smoe_hip.h: smoe_sample_area) -- the one host
+    statement of the arithmetic, in float32 throughout, as the kernel computes it.  ``points`` ``[N, d]``: the cell centres in
+    source pixels; ``footprint`` ``[d, d]``: column ``m`` is the edge vector of an output cell along view axis ``m``;
+    ``taps``: the taps per view axis (1 .. 16, product at most 64).  Tap ``j`` (row-major, last axis fastest) has the offset
+    ``o_m = float32(2 j_m + 1 - taps[m]) / float32(2 taps[m])`` and the position ``t_l = x_l``, then for ``m = 0 .. d-1``:
+    ``t_l = t_l + (F[l][m] * o_m)``, the product and the sum rounded separately.  Returns float32 ``[N, T, d]``."""
+    pts = np.asarray(points, dtype=np.float32)
+    if pts.ndim != 2:
+        raise ValueError("area_taps: points must be [N, d]")
+    d = pts.shape[1]
+    F, tp = area_args(footprint, taps, d)
+    off = [(np.arange(n, dtype=np.int64) * 2 + 1 - n).astype(np.float32) / np.float32(2 * n) for n in tp]
+    jj = np.stack(np.meshgrid(*[np.arange(n) for n in tp], indexing="ij"), axis=-1).reshape(-1, d)       # [T, d] row-major
+    out = np.empty((pts.shape[0], jj.shape[0], d), dtype=np.float32)
+    for l in range(d):
+        t = np.repeat(pts[:, l:l + 1], jj.shape[0], axis=1)
+        for m in range(d):
+            t = (t + (F[l, m] * off[m][jj[:, m]]).astype(np.float32)[None, :]).astype(np.float32)
+        out[:, :, l] = t
+    return out
+
+
+def footprint_taps(footprint):
+    """``taps="auto"`` of ``Smoe.sample_area``: one tap per source pixel the cell covers along each view axis,
+    ``n_m = clamp(ceil(max_l |F[l][m]|), 1, 16)``, then the largest entry (the first of equals) is decremented until the
+    product is at most 64.  Returns a tuple of ints."""
+    F = np.asarray(footprint, dtype=np.float64)
+    if F.ndim != 2 or F.shape[0] != F.shape[1] or not np.isfinite(F).all():
+        raise ValueError("footprint_taps: footprint must be a finite [d, d] array")
+    tp = [int(min(max(math.ceil(float(np.abs(F[:, m]).max())), 1), AREA_AXIS_TAPS)) for m in range(F.shape[1])]
+    while int(np.prod(tp)) > AREA_TAPS:
+        tp[int(np.argmax(tp))] -= 1
+    return tuple(tp)
 
 
 def to_planar(blocks: np.ndarray) -> np.ndarray:

@@ -214,6 +214,23 @@ struct SampleGradArgs {
     float du_dx[SMOE_MAX_DIM];       // block units per source pixel, 1 / (n - 1); 0 on an axis of one pixel per block
 };
 
+// smoe_sample_area (smoe_sample_area.hip.h): the mean of the model over a regular grid of taps inside the footprint of every
+// point.  s: the cell centres, the blocks and the blend as for smoe_sample; s.r.image / s.r.fmt: the lattice values [N, C] or
+// null; s.r.argmax is not used; s.block: the centre's own block [N] or null.
+constexpr int SAMPLE_AREA_AXIS_TAPS = 16;       // taps per axis, at most
+constexpr int SAMPLE_AREA_TAPS = 64;            // taps per point, at most
+struct SampleAreaArgs {
+    SampleArgs s;
+    float F[SMOE_MAX_DIM * SMOE_MAX_DIM];       // the footprint [dim, dim] row-major, source pixels: column m = the cell's edge along view axis m
+    int taps[SMOE_MAX_DIM];                     // taps per view axis (1 on the axes past dim)
+    int ntaps;                                  // their product
+    float half[SMOE_MAX_DIM];                   // half extent of the footprint per source axis, 0.5 sum_m |F[l][m]|, rounded up
+    float* mean;              // [N, C] the mean before the lattice, or null
+    uint8_t* count;           // [N] taps inside the image, or null
+    int vec_mean, vec_cnt;    // the plane's base is 16-byte aligned: vector stores
+    int off_tap;              // float offset of the tap table in the dynamic LDS (launcher)
+};
+
 // What the launcher of a block decoder derives from checked arguments, next to the geometry fields of RenderArgs (and off_w
 // of RenderBlendArgs) it fills: a pure host computation (render_layout / render_blend_layout), also run without a device
 struct RenderLayout {
@@ -267,6 +284,9 @@ struct Variant {
     // point derivative (smoe_sample_grad.hip.h), same conventions
     hipError_t (*sample_grad_layout)(SampleGradArgs&, long long records, RenderLayout&);
     hipError_t (*sample_grad)(const SampleGradArgs&, const RenderLayout&, hipStream_t);
+    // area-averaged point decoder (smoe_sample_area.hip.h), same conventions
+    hipError_t (*sample_area_layout)(SampleAreaArgs&, long long records, RenderLayout&);
+    hipError_t (*sample_area)(const SampleAreaArgs&, const RenderLayout&, hipStream_t);
 };
 
 // ---- shared-kernel image mode (smoe_shared.hip) ----------------------------------------------

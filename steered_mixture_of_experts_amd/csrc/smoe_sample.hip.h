@@ -55,6 +55,10 @@ __device__ __forceinline__ bool sample_resolve(float x, int n, float len, int& g
     return true;
 }
 
+// A value before the lattice onto the 8-bit lattice: its index (the value is index * kc.scale).  The one rounding of the
+// point decoders' own results: sample_kernel's cross-fade and sample_area_kernel's mean (smoe_sample_area.hip.h).
+__device__ __forceinline__ float lattice_index(const KernelConsts& kc, float v) { return floorf(fmaf(v, kc.inv_scale, 0.5f)); }
+
 // What every lane of render_kernel does for its block, from global memory: the block image (packed parameters, `active`
 // flags), the fake-quantised variables, the derived constants.  id: image-wide block index.
 template <int D, int C, int K, bool QUANT, bool IC>
@@ -145,14 +149,14 @@ __device__ __forceinline__ void point_fetch(const SampleArgs& s, bool staged, co
     else sample_derive<D, C, K, QUANT, IC>(s.r, id, B);
 }
 
-// Point i: false where it is outside (id -1).  Otherwise its block g, its block-unit coordinates x, the block's image-wide
-// index id and its record's index rec in the box.
+// The position pt in source pixels: false where it is outside (id -1).  Otherwise its block g, its block-unit coordinates x,
+// the block's image-wide index id and its record's index rec in the box.
 template <int D>
-__device__ __forceinline__ bool point_locate(const SampleArgs& s, const int (&lo)[D], const int (&nbx)[D], long long i,
-                                             int (&g)[D], float (&x)[D], long long& id, int& rec) {
+__device__ __forceinline__ bool point_locate_at(const SampleArgs& s, const int (&lo)[D], const int (&nbx)[D], const float (&pt)[D],
+                                                int (&g)[D], float (&x)[D], long long& id, int& rec) {
     bool in = true;
 #pragma unroll
-    for (int l = 0; l < D; ++l) in = sample_resolve(s.points[i * D + l], s.n[l], s.length[l], g[l], x[l]) && in;
+    for (int l = 0; l < D; ++l) in = sample_resolve(pt[l], s.n[l], s.length[l], g[l], x[l]) && in;
     id = -1;
     rec = 0;
     if (in) {
@@ -164,6 +168,16 @@ __device__ __forceinline__ bool point_locate(const SampleArgs& s, const int (&lo
         }
     }
     return in;
+}
+
+// point i of the list
+template <int D>
+__device__ __forceinline__ bool point_locate(const SampleArgs& s, const int (&lo)[D], const int (&nbx)[D], long long i,
+                                             int (&g)[D], float (&x)[D], long long& id, int& rec) {
+    float pt[D];
+#pragma unroll
+    for (int l = 0; l < D; ++l) pt[l] = s.points[i * D + l];
+    return point_locate_at<D>(s, lo, nbx, pt, g, x, id, rec);
 }
 
 // The neighbour window of axis l at coordinate x in block g: the signed weight w (> 0: towards the high neighbour), the
@@ -376,7 +390,7 @@ __global__ void __launch_bounds__(RENDER_THREADS) sample_kernel(SampleArgs s) {
 #pragma unroll
                         for (int c = 0; c < C; ++c) {
                             const float val = (den > 0.0f) ? num[c] / den : 0.0f;
-                            po.kq[c] = floorf(fmaf(val, a.kc.inv_scale, 0.5f));
+                            po.kq[c] = lattice_index(a.kc, val);
                             po.q[c] = po.kq[c] * a.kc.scale;
                         }
                     }

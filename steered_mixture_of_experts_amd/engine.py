@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import blocks as blk
 
 PARAM_NAMES = ("pis", "musX", "A_diagonal", "A_corr", "gamma_e", "nu_e")
 
@@ -496,6 +497,41 @@ class BlockEngine(_Engine):
                                            self._stream())
         _lib.check(rc)
         res = (out,) + ((val,) if want_values else ()) + ((bk,) if want_block else ())
+        return res if len(res) > 1 else out
+
+    def sample_area(self, params, active, grid, length, points, footprint, taps, blend=None, out=None, dtype=torch.float32,
+                    want_mean=False, want_count=False, want_block=False, center_grid=None):
+        """Anti-aliased point decode (include/smoe_hip.h: smoe_sample_area): per point -- the centre of an output cell, as
+        ``sample``'s points -- the mean of the model over a regular grid of ``taps[m]`` taps along view axis ``m`` inside the
+        cell's ``footprint`` (host ``[d, d]``, column ``m`` = the cell's edge vector along view axis ``m`` in source pixels;
+        ``blocks.area_taps`` states the positions), put on the lattice, into ``[N, C]``.  Taps outside the image are left out
+        of the mean.  ``params``, ``active``, ``center_grid`` and ``blend`` are ``sample``'s.  Returns the lattice values, then
+        with ``want_mean`` the float32 means before the lattice ``[N, C]``, with ``want_count`` the uint8 number of taps
+        inside ``[N]`` and with ``want_block`` the int32 own block of the centre ``[N]`` (-1: outside)."""
+        who = "sample_area"
+        grid, length = [int(g) for g in grid], [int(v) for v in length]
+        if dtype not in (torch.float32, torch.uint8):
+            raise ValueError(f"{who}: dtype must be torch.float32 or torch.uint8")
+        N, bl = self._check_point_args(who, params, active, grid, length, points, blend)
+        d = self.cfg.dim
+        try:
+            F, tp = blk.area_args(footprint, taps, d)
+        except ValueError as e:
+            raise ValueError(f"{who}: {e}") from None
+        out = self._point_out(who, out, (N, self.cfg.channels), dtype, dtype)
+        fmt = _lib.SMOE_IMAGE_U8 if dtype == torch.uint8 else _lib.SMOE_IMAGE_F32
+        mean = torch.empty((N, self.cfg.channels), dtype=torch.float32, device=self.device) if want_mean else None
+        cnt = torch.empty((N,), dtype=torch.uint8, device=self.device) if want_count else None
+        bk = torch.empty((N,), dtype=torch.int32, device=self.device) if want_block else None
+        cp = self._cparams(params)
+        with self._center_grid_installed(center_grid):
+            rc = self.lib.smoe_sample_area(self._h, C.byref(cp), _ptr(active), _slots(C.c_int32, grid, 1),
+                                           _slots(C.c_int32, length, 1), _ptr(points), N,
+                                           (C.c_float * (d * d))(*[float(v) for v in F.reshape(-1)]), (C.c_int32 * d)(*tp),
+                                           None if bl is None else _slots(C.c_float, bl, 0.0), _ptr(out), fmt, _ptr(mean),
+                                           _ptr(cnt), _ptr(bk), self._stream())
+        _lib.check(rc)
+        res = (out,) + ((mean,) if want_mean else ()) + ((cnt,) if want_count else ()) + ((bk,) if want_block else ())
         return res if len(res) > 1 else out
 
     def fit(self, target, params, state: AdamState, active, n_iters: int, loss_w=None, diverged=None,

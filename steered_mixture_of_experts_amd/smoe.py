@@ -807,7 +807,7 @@ class Smoe(_SmoeBase):
         return self._render(scale, samples_per_block, dtype, quantized, want_argmax, to_host, blend=bl)
 
     def render_view(self, window, size=None, scale=None, dtype=np.float32, quantized=False, want_argmax=False,
-                    to_host=True, blend=0.0):
+                    to_host=True, blend=0.0, taps=None):
         """Decode a viewport: the axis-aligned ``window`` of the image domain at the output ``size``, on the device (the
         engine's ``render_view``; include/smoe_hip.h: smoe_render_view).  Only the window is computed and stored: an 8x
         detail, a fit-to-window zoom of any ratio, a thumbnail with fewer samples than blocks, one frame of a video.
@@ -818,7 +818,11 @@ class Smoe(_SmoeBase):
         ``dtype``, ``quantized``, ``blend`` and the global ids of ``want_argmax`` (int64, -1: none) are ``render``'s; the
         kernel lists are ``render``'s too.  Returns the image ``[*E, C]``.  Several ranks: parameters and lists are gathered
         and every rank renders the whole view (a view is small); the result is the same on every rank and for every
-        number of ranks."""
+        number of ranks.
+        ``taps``: None (the default) or all ones: one position per sample, as above.  Otherwise (a number, one per axis or
+        ``"auto"``) every sample is the mean over ``taps[l]`` taps per axis inside its cell -- ``sample_area`` at the same
+        positions ``x_i`` (rounded to float32 once) with the footprint ``diag((hi - lo) / E)``: a thumbnail that does not
+        alias.  ``want_argmax`` is refused then (an average has no single kernel)."""
         d, n = self.dim_domain, self.batch_size_valued
         bl = self._blend_arg("render_view", blend)
         window = [None] * d if window is None else list(window)
@@ -845,6 +849,14 @@ class Smoe(_SmoeBase):
         if npdt not in (np.dtype(np.float32), np.dtype(np.uint8)):
             raise ValueError("render_view: dtype must be float32 or uint8")
         tdt = torch.uint8 if npdt == np.dtype(np.uint8) else torch.float32
+        foot = np.diag([(hi - lo) / e for (lo, hi), e in zip(win, E)])
+        tp = self._taps_arg("render_view", taps, foot)
+        if tp is not None:
+            if want_argmax:
+                raise ValueError("render_view: want_argmax needs taps=None (an average has no single kernel)")
+            axes = [blk.view_positions(lo, hi, e) for (lo, hi), e in zip(win, E)]     # view_axis' x_i, rounded once
+            pts = np.stack(np.meshgrid(*axes, indexing="ij"), axis=-1)
+            return self.sample_area(pts, foot, taps=tp, dtype=dtype, quantized=quantized, to_host=to_host, blend=blend)
         eng = self._engine
         if not hasattr(eng, "render_view"):
             raise NotImplementedError("this engine has no render_view()")
@@ -939,12 +951,74 @@ class Smoe(_SmoeBase):
             ids = None if ids is None else ids.cpu().numpy()
         return (img, ids) if want_argmax else img
 
-    def render_warp(self, matrix, size, **options):
+    def render_warp(self, matrix, size, taps=None, **options):
         """An affine view of the model: ``sample(blocks.warp_points(matrix, size), **options)``.  ``matrix = [M | t]``
         ``[d, d + 1]`` maps the cell centre ``i + 0.5`` of output index ``i`` to the source position ``M (i + 0.5) + t`` in
         source pixels -- a rotation, a shear, any zoom.  Returns the image ``[*size, C]`` (0 where the view leaves the image);
-        ``options`` are ``sample``'s."""
-        return self.sample(blk.warp_points(matrix, size), **options)
+        ``options`` are ``sample``'s.  ``taps``: None (the default) or all ones: that call.  Otherwise (a number, one per view
+        axis or ``"auto"``) ``sample_area`` at the same positions with the footprint ``M`` -- a zoomed-out warp that does not
+        alias; ``options`` are ``sample_area``'s then."""
+        pts = blk.warp_points(matrix, size)
+        M = np.asarray(matrix, dtype=np.float64)[:, :self.dim_domain]
+        tp = self._taps_arg("render_warp", taps, M)
+        if tp is None:
+            return self.sample(pts, **options)
+        return self.sample_area(pts, M, taps=tp, **options)
+
+    def _taps_arg(self, who, taps, footprint):
+        """``taps`` of ``render_view`` / ``render_warp`` / ``sample_area`` as one int per view axis (``"auto"``:
+        ``blocks.footprint_taps``), or None where there is nothing to average: ``taps`` None or all ones."""
+        if taps is None:
+            return None
+        if isinstance(taps, str):
+            if taps != "auto":
+                raise ValueError(f'{who}: taps must be "auto", a number or one per axis')
+            tp = list(blk.footprint_taps(footprint))
+        else:
+            try:
+                _, tp = blk.area_args(footprint, taps, self.dim_domain)
+            except ValueError as e:
+                raise ValueError(f"{who}: {e}") from None
+        return None if all(v == 1 for v in tp) else tp
+
+    def sample_area(self, points, footprint, taps="auto", dtype=np.float32, quantized=False, want_mean=False, want_count=False,
+                    to_host=True, blend=0.0):
+        """Anti-aliased ``sample``, on the device (the engine's ``sample_area``; include/smoe_hip.h: smoe_sample_area): every
+        point is the centre of an output cell, and its result is the mean of the model over a regular grid of taps inside the
+        cell, put on the lattice -- a decode coarser than the source (a thumbnail, a zoomed-out warp) takes one position per
+        cell with ``sample`` and aliases.  ``footprint`` ``[d, d]`` in source pixels: column ``m`` is the edge vector of a cell
+        along view axis ``m`` (``M`` of an affine view, ``diag((hi - lo) / E)`` of a viewport); one footprint serves all
+        points.  ``taps``: a number, one per view axis (1 .. 16, product at most 64) or ``"auto"``
+        (``blocks.footprint_taps``: one tap per source pixel covered).  Positions: ``blocks.area_taps``.  Taps outside the
+        image are left out of the mean, so an edge cell stays as bright as an inside one; a cell with no tap inside gives 0.
+        ``points``, ``dtype``, ``quantized``, ``blend`` and the kernel lists are ``sample``'s.  Returns ``[..., C]``; with
+        ``want_mean`` also the float32 means before the lattice ``[..., C]``, with ``want_count`` the uint8 number of taps
+        inside ``[...]``.  ``to_host=False`` returns device tensors.  Several ranks: as ``sample``.  Per-block models only:
+        ``SharedSmoe`` has no counterpart."""
+        d = self.dim_domain
+        bl = self._blend_arg("sample_area", blend)
+        npdt = np.dtype(dtype)
+        if npdt not in (np.dtype(np.float32), np.dtype(np.uint8)):
+            raise ValueError("sample_area: dtype must be float32 or uint8")
+        tdt = torch.uint8 if npdt == np.dtype(np.uint8) else torch.float32
+        tp = self._taps_arg("sample_area", taps, footprint) or [1] * d
+        eng = self._engine
+        if not hasattr(eng, "sample_area"):
+            raise NotImplementedError("this engine has no sample_area()")
+        dev = eng.device
+        pts, lead = self._points_arg("sample_area", points, dev)
+        params, active, center = self._whole_model(quantized)
+        res = eng.sample_area(params, active, self.grid, [int(v) for v in self.image.shape[:d]], pts, footprint, tp,
+                              blend=bl, dtype=tdt, want_mean=want_mean, want_count=want_count, center_grid=center)
+        res = list(res) if isinstance(res, tuple) else [res]
+        res[0] = res[0].reshape(lead + (self.channels,))
+        if want_mean:
+            res[1] = res[1].reshape(lead + (self.channels,))
+        if want_count:
+            res[-1] = res[-1].reshape(lead)
+        if to_host:
+            res = [t.cpu().numpy() for t in res]
+        return tuple(res) if len(res) > 1 else res[0]
 
     def sample_grad(self, points, quantized=False, want_values=False, to_host=True, blend=0.0):
         """The model's exact spatial derivative at arbitrary positions, on the device (the engine's ``sample_grad``;

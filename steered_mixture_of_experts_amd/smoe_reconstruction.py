@@ -14,6 +14,9 @@ window; ``--window`` absent: the whole image); they work together with ``--scale
 ``--affine M.. T..`` (``d (d + 1)`` numbers, row-major ``[M | t]``) with ``--size`` decodes an affine view with
 ``Smoe.render_warp``: output cell centre ``i + 0.5`` shows the source position ``M (i + 0.5) + t`` (source pixels), a rotation
 or a shear included; it works with ``--blend``, not with ``--window`` / ``--frames`` / ``--scale``; per-block models only.
+``--taps N ...`` (one number or one per axis) or ``--taps auto`` with ``--affine`` or ``--window`` / ``--size`` averages every
+output sample over that many taps per axis inside its cell (``Smoe.sample_area``): a view coarser than the source that does
+not alias; per-block models only.
 """
 import argparse
 import os
@@ -46,12 +49,19 @@ _shared_engine_factory = None      # tests put the oracle-backed engine here; No
 
 
 def main(image_path, results_path, params_file, batches=1, bit_depths=(20, 18, 6, 10, 10), quant_params=False,
-         scale=None, frames=None, blend=None, window=None, size=None, affine=None):
+         scale=None, frames=None, blend=None, window=None, size=None, affine=None, taps=None):
     if len(bit_depths) != 5:
         raise ValueError("Number of bit depths must be five!")           # smoe_reconstruction.py:17-18
     orig, precision, _ = read_image(image_path)
     cp = load_checkpoint(params_file)
     init_params = cp['params']
+    tp = _taps_option(taps)
+    if tp is not None:
+        if np.asarray(init_params['pis']).ndim == 1:
+            raise ValueError("--taps needs a per-block model: this pickle holds a whole-image (shared-kernel) model, which "
+                             "has no area-averaged decoder")
+        if affine is None and window is None and size is None:
+            raise ValueError("--taps needs --affine or --window / --size (the view whose cells are averaged)")
     if results_path is not None and not os.path.exists(results_path):
         os.mkdir(results_path)
     # the graph the model was trained on (smoe_reconstruction.py:32-43 copies these from the pickle onto the model; here
@@ -105,8 +115,8 @@ def main(image_path, results_path, params_file, batches=1, bit_depths=(20, 18, 6
         if len(size) != d:
             raise ValueError(f"--size takes one number per axis ({d})")
         reconstruction = smoe.render_warp(np.asarray(affine, dtype=np.float64).reshape(d, d + 1), [int(v) for v in size],
-                                          quantized=with_q, blend=bl)
-        reconstruction_path += "_warp" + "x".join(str(v) for v in reconstruction.shape[:d])
+                                          quantized=with_q, blend=bl, taps=tp)
+        reconstruction_path += "_warp" + "x".join(str(v) for v in reconstruction.shape[:d]) + _taps_suffix(tp)
         if any(v != 0.0 for v in bl):
             reconstruction_path += "_blend" + "x".join("%g" % v for v in bl)
     elif window is not None or size is not None:
@@ -127,8 +137,8 @@ def main(image_path, results_path, params_file, batches=1, bit_depths=(20, 18, 6
             raise ValueError(f"--scale takes one value or {d}")
         win = None if window is None else [(float(window[2 * l]), float(window[2 * l + 1])) for l in range(d)]
         reconstruction = smoe.render_view(win, size=None if size is None else [int(v) for v in size],
-                                          scale=None if size is not None else sc, quantized=with_q, blend=bl)
-        reconstruction_path += "_view" + "x".join(str(v) for v in reconstruction.shape[:d])
+                                          scale=None if size is not None else sc, quantized=with_q, blend=bl, taps=tp)
+        reconstruction_path += "_view" + "x".join(str(v) for v in reconstruction.shape[:d]) + _taps_suffix(tp)
         if any(v != 0.0 for v in bl):
             reconstruction_path += "_blend" + "x".join("%g" % v for v in bl)
     elif frames is not None or any(v != 1.0 for v in sc) or any(v != 0.0 for v in bl):
@@ -149,6 +159,25 @@ def main(image_path, results_path, params_file, batches=1, bit_depths=(20, 18, 6
             reconstruction_path += "_blend" + "x".join("%g" % v for v in bl)
     write_image(reconstruction, reconstruction_path, smoe.dim_domain, smoe.use_yuv, precision)
     return reconstruction, loss, mse
+
+
+def _taps_option(taps):
+    """``--taps``: None, ``"auto"`` or a list of ints"""
+    if taps is None:
+        return None
+    vals = [taps] if isinstance(taps, (str, int)) else list(taps)
+    if len(vals) == 1 and str(vals[0]) == "auto":
+        return "auto"
+    try:
+        return [int(v) for v in vals]
+    except (TypeError, ValueError):
+        raise ValueError("--taps takes auto, one number or one per axis") from None
+
+
+def _taps_suffix(tp):
+    if tp is None:
+        return ""
+    return "_taps" + ("auto" if tp == "auto" else "x".join(str(v) for v in tp))
 
 
 def _parser():
@@ -172,6 +201,10 @@ def _parser():
     parser.add_argument('--affine', type=float, default=None, nargs='+',
                         help="decode an affine view of --size samples: the d (d + 1) numbers of [M | t], row-major; output "
                              "cell centre i + 0.5 shows source position M (i + 0.5) + t (per-block models only)")
+    parser.add_argument('--taps', type=str, default=None, nargs='+',
+                        help="with --affine or --window / --size: average every output sample over this many taps per axis "
+                             "inside its cell (one number, one per axis, or auto = one per source pixel covered; 1 .. 16 each, "
+                             "at most 64 in all; per-block models only)")
     return parser
 
 
