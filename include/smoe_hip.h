@@ -386,7 +386,7 @@ int smoe_sample_grad(smoe_handle h, const smoe_params* p, const uint32_t* active
  * No argmax: an average has no single kernel.  The result for a point depends on its coordinates, footprint, taps and the
  * model only: not on num_points, its place in the list, the other points, staging or how the launch is cut.
  * Limits: one footprint per call (an affine view); at most 64 taps (an 8 x 8 box: a 1/8 thumbnail; 4 x 4 x 4: video);
- * per-block models only -- there is no counterpart for the whole-image models of smoe_shared_sample.
+ * per-block models only -- the counterpart for the whole-image models of smoe_shared_sample is smoe_shared_sample_area.
  * A workgroup takes 256 consecutive points and bounds the blocks of all their taps: the centres' box widened per axis by the
  * footprint's half extent 0.5 sum_m |F[l][m]| plus one block (with blend: one more); records are staged as in smoe_sample where
  * that box fits the budget (SMOE_SAMPLE_RECORDS applies), and both paths give the same bits.  Offsets are 64-bit; stores are 16
@@ -633,6 +633,54 @@ int smoe_shared_render_view_grad(smoe_shared_handle h, const smoe_params* p, con
                                  const int32_t extent[3], const float* const axis_coords[3],
                                  const int32_t* const axis_batch[3],
                                  float* jac, float* values, int32_t* batch, void* stream);
+
+/* Anti-aliased decode of a whole-image model: per point -- the centre of an output cell -- the mean of the model over a small
+ * regular grid of taps inside the cell's footprint, every tap with the kernel list of the batch that owns IT: smoe_sample_area
+ * for the shared-kernel mode.  A thumbnail or a zoomed-out warp taken with smoe_shared_sample aliases; this integrates.
+ *   p, lists, points, num_points   as in smoe_shared_sample (lists covers ALL batches, NULL = every kernel); a point is the
+ *                            centre of an output cell
+ *   footprint                HOST [dim, dim] fp32, row-major, source pixels: column m is the edge vector of an output cell along
+ *                            view axis m (an affine view x = M i + t: footprint = M).  One footprint serves all points of a call
+ *   taps                     HOST [dim] int32, 1 <= taps[m] <= 16, prod(taps) <= 64: the taps along view axis m
+ *   values                   DEVICE [num_points, C] or NULL, SMOE_IMAGE_F32 (lattice values) or SMOE_IMAGE_U8 (lattice indices)
+ *   mean                     DEVICE [num_points, C] fp32 or NULL: the mean before the lattice
+ *   count                    DEVICE [num_points] uint8 or NULL: the taps inside the image
+ *   batch                    DEVICE [num_points] int32 or NULL: global id of the batch that owns the CENTRE, -1 = centre outside
+ *                            (a centre outside with taps inside still gets their mean)
+ * Definition, per point x and tap multi-index j (0 <= j_m < taps[m]), all in IEEE fp32:
+ *   tap offset               o_m = (float)(2 j_m + 1 - taps[m]) / (float)(2 taps[m]): an exact integer numerator, one correctly
+ *                            rounded division
+ *   tap position             t_l = x_l, then for m = 0 .. dim-1: t_l = t_l + (F[l][m] * o_m), product and sum rounded separately
+ *                            (never fused): exactly smoe_sample_area's, blocks.area_taps gives the position bit for bit
+ *   tap value                the tap is resolved exactly as a point of smoe_shared_sample_grad: the outside rule against
+ *                            image_shape, the owning batch, u = (t - 0.5f) / (float)(S - 1) (0 for S == 1), the compacted
+ *                            list of THAT batch, the gate sums and the clip as the same statements in the same order; its value
+ *                            is that call's `values` V (before the lattice), bit for bit
+ *   mean                     acc_c = 0, cnt = 0; over the taps in row-major order of j (last axis fastest) an inside tap adds
+ *                            acc_c = acc_c + V_c (one fp32 add) and cnt += 1; mean_c = acc_c / (float)cnt, correctly rounded;
+ *                            cnt == 0 gives 0.  Taps outside the image are left out, not counted as black.  The order is
+ *                            smoe_sample_area's and does not depend on which batches the taps fall in
+ *   values                   the mean put on the lattice by the statement smoe_shared_sample ends with,
+ *                            floorf(fmaf(mean, inv_scale, 0.5f)), times scale for SMOE_IMAGE_F32, the index for SMOE_IMAGE_U8:
+ *                            with one tap smoe_shared_sample's image bit for bit.  Every V is at most nudged_max, but the
+ *                            rounded sum of up to 64 of them over their count may pass nudged_max by a few ulp, so the index is
+ *                            clamped to the index of nudged_max (no change wherever the mean is within the clip)
+ * No argmax: an average has no single kernel.  A point's result depends only on its coordinates, the footprint, the taps, the
+ * model and the lists of the batches its taps lie in: not on num_points, its place in the list, the other points or the cut of
+ * the launch.  With T = prod(taps) a workgroup takes 512 / T consecutive points, one tap per work item, and walks the distinct
+ * batches among their taps as smoe_shared_sample does; there is no table form (a viewport goes through the point form).
+ * Offsets are 64-bit; stores are 16 bytes wide where values / mean / count / batch are 16-byte aligned, element-wise at ragged
+ * heads and tails.
+ * num_points == 0 is a successful no-op.  SMOE_ERR_INVALID names the offending argument: smoe_shared_sample's cases (values
+ * excepted: a null handle or p, a bad image_format, num_points < 0, with num_points > 0 a null points), a null footprint / taps,
+ * a non-finite footprint entry, taps[m] outside 1 .. 16, prod(taps) > 64, (num_points > 0) values and mean both NULL.
+ * SMOE_ERR_UNSUPPORTED: image_shape[l] > 2^24, SMOE_IMAGE_U8 values with precision > 8, 2^31 or more workgroups, more than
+ * 160 KB of LDS. */
+int smoe_shared_sample_area(smoe_shared_handle h, const smoe_params* p, const uint32_t* lists,
+                            const float* points, int64_t num_points,
+                            const float* footprint, const int32_t* taps,
+                            void* values, int32_t image_format,
+                            float* mean, uint8_t* count, int32_t* batch, void* stream);
 
 /* run_batched(train=True) minus train_op: forward + tf.gradients of the batches, accumulated into
  * the handle's gradient buffer (accum_ops, smoe.py:1150); kernel lists pruned (smoe.py:1763-1766).

@@ -380,6 +380,21 @@ struct SharedSampleGradArgs {
     float du_dx[SMOE_MAX_DIM];        // 1 / (image_shape[l] - 1), 0 for an axis of one pixel
 };
 
+// smoe_shared_sample_area (smoe_shared_sample_area.hip.h): the mean of the model over a regular grid of taps inside the
+// footprint of every point of `s` (list mode only), every tap with the list of the batch that owns it.  s.image / s.fmt: the
+// lattice values [N, C] or null; s.argmax is not used.
+struct SharedSampleAreaArgs {
+    SharedSampleArgs s;
+    float F[SMOE_MAX_DIM * SMOE_MAX_DIM];       // the footprint [dim, dim] row-major, source pixels: column m = the cell's edge along view axis m
+    int taps[SMOE_MAX_DIM];                     // taps per view axis (1 on the axes past dim)
+    int ntaps;                                  // their product T, 1 .. SAMPLE_AREA_TAPS
+    int ppw;                                    // points per workgroup, SSA_TILE / T (launcher)
+    float* mean;              // [N, C] the mean before the lattice, or null
+    uint8_t* count;           // [N] taps inside the image, or null
+    int32_t* batch;           // [N] global id of the batch that owns the centre, -1 = centre outside; or null
+    int vec_mean, vec_cnt, vec_bat;   // the plane's base is 16-byte aligned: vector stores
+};
+
 // Per-kernel sum over the batches of the current pass, in a fixed order (lane = batch mod 64 ascending, then a butterfly
 // over the lanes): racc[k][PK] and nact[k] are OVERWRITTEN -- bit-identical from run to run and for every split of the
 // batches of a rank over smoe_shared_accumulate calls.
@@ -464,6 +479,9 @@ hipError_t launch_shared_sample(const SharedSampleArgs& a, int D, int C, bool gr
 // the same pair for smoe_shared_sample_grad / smoe_shared_render_view_grad
 hipError_t shared_sample_grad_layout(int D, int C, int K, long long num_points, RenderLayout& g);
 hipError_t launch_shared_sample_grad(const SharedSampleGradArgs& q, int D, int C, bool grid, const RenderLayout& g, hipStream_t st);
+// the same pair for smoe_shared_sample_area; T = prod(taps), 1 .. SAMPLE_AREA_TAPS.  The launch fills q.ppw
+hipError_t shared_sample_area_layout(int D, int C, int K, int T, long long num_points, RenderLayout& g);
+hipError_t launch_shared_sample_area(const SharedSampleAreaArgs& q, int D, int C, const RenderLayout& g, hipStream_t st);
 
 const Variant* variants(int* count);
 hipError_t launch_readmit(const ReadmitArgs& a, int D, hipStream_t st);

@@ -1146,6 +1146,8 @@ __global__ void shared_readmit_kernel(SharedReadmitArgs a) {
 #include "smoe_shared_sample.hip.h"
 // and the spatial derivative at the same points (shared_sample_grad_kernel, launch_shared_sample_grad)
 #include "smoe_shared_sample_grad.hip.h"
+// and the area-averaged decode at the same points (shared_sample_area_kernel, launch_shared_sample_area)
+#include "smoe_shared_sample_area.hip.h"
 
 namespace smoe {
 

@@ -789,6 +789,36 @@ class SharedEngine(_Engine):
         res = (out,) + ((val,) if want_values else ()) + ((bk,) if want_batch else ())
         return res if len(res) > 1 else out
 
+    def sample_area(self, params, lists, points, footprint, taps, out=None, dtype=torch.float32, want_mean=False,
+                    want_count=False, want_batch=False):
+        """Anti-aliased point decode (include/smoe_hip.h: smoe_shared_sample_area): per point -- the centre of an output cell,
+        as ``sample``'s points -- the mean of the model over a regular grid of ``taps[m]`` taps along view axis ``m`` inside
+        the cell's ``footprint`` (host ``[d, d]``, column ``m`` = the cell's edge vector along view axis ``m`` in source
+        pixels; ``blocks.area_taps`` states the positions), every tap with the kernel list of the batch that owns it, put on
+        the lattice, into ``[N, C]``.  Taps outside the image are left out of the mean.  ``lists`` as in ``sample``.  Returns
+        the lattice values, then with ``want_mean`` the float32 means before the lattice ``[N, C]``, with ``want_count`` the
+        uint8 number of taps inside ``[N]`` and with ``want_batch`` the int32 global id of the batch that owns the centre
+        ``[N]`` (-1: outside)."""
+        who = "sample_area"
+        N = self._check_points(who, points, lists)
+        d = self.cfg.dim
+        try:
+            F, tp = blk.area_args(footprint, taps, d)
+        except ValueError as e:
+            raise ValueError(f"{who}: {e}") from None
+        out, fmt, _ = self._dense_planes(who, (N,), out, dtype, False)
+        mean = torch.empty((N, self.cfg.channels), dtype=torch.float32, device=self.device) if want_mean else None
+        cnt = torch.empty((N,), dtype=torch.uint8, device=self.device) if want_count else None
+        bk = torch.empty((N,), dtype=torch.int32, device=self.device) if want_batch else None
+        if N > 0:
+            cp = self._cparams(params)
+            _lib.check(self.lib.smoe_shared_sample_area(self._h, C.byref(cp), _ptr(lists), _ptr(points), N,
+                                                        (C.c_float * (d * d))(*[float(v) for v in F.reshape(-1)]),
+                                                        (C.c_int32 * d)(*tp), _ptr(out), fmt, _ptr(mean), _ptr(cnt), _ptr(bk),
+                                                        self._stream()))
+        res = (out,) + ((mean,) if want_mean else ()) + ((cnt,) if want_count else ()) + ((bk,) if want_batch else ())
+        return res if len(res) > 1 else out
+
     def render_view_grad(self, params, lists, axes, batches, out=None, want_values=False, want_batch=False):
         """Viewport derivative (include/smoe_hip.h: smoe_shared_render_view_grad): ``sample_grad`` on the dense view of
         ``render_view``'s tables, ``[*E, d, C]``; the other planes ``[*E, C]`` and ``[*E]``."""

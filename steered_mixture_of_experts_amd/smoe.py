@@ -298,6 +298,23 @@ class _SmoeBase:
         return {k: torch.from_numpy(v).to(self._engine.device) for k, v in self._local_rparams().items()}
 
     # -- decoding on another grid -------------------------------------------------------------
+    def _taps_arg(self, who, taps, footprint):
+        """``taps`` of ``render_view`` / ``render_warp`` / ``sample_area`` (``SharedSmoe``: ``eval_view`` / ``eval_warp`` /
+        ``eval_points_area``) as one int per view axis (``"auto"``: ``blocks.footprint_taps``), or None where there is
+        nothing to average: ``taps`` None or all ones."""
+        if taps is None:
+            return None
+        if isinstance(taps, str):
+            if taps != "auto":
+                raise ValueError(f'{who}: taps must be "auto", a number or one per axis')
+            tp = list(blk.footprint_taps(footprint))
+        else:
+            try:
+                _, tp = blk.area_args(footprint, taps, self.dim_domain)
+            except ValueError as e:
+                raise ValueError(f"{who}: {e}") from None
+        return None if all(v == 1 for v in tp) else tp
+
     def _render(self, scale, samples_per_block, dtype, quantized, want_argmax, to_host, use_lists=True, blend=None):
         """``render`` of both modes.  Hooks: ``_local_rparams``, ``_render_lists(quantized)``, ``_render_grid(m)`` ->
         (tile grid, output extent, one sample table per axis), ``_engine_render`` and, with ``_block_local_ids``,
@@ -965,22 +982,6 @@ class Smoe(_SmoeBase):
             return self.sample(pts, **options)
         return self.sample_area(pts, M, taps=tp, **options)
 
-    def _taps_arg(self, who, taps, footprint):
-        """``taps`` of ``render_view`` / ``render_warp`` / ``sample_area`` as one int per view axis (``"auto"``:
-        ``blocks.footprint_taps``), or None where there is nothing to average: ``taps`` None or all ones."""
-        if taps is None:
-            return None
-        if isinstance(taps, str):
-            if taps != "auto":
-                raise ValueError(f'{who}: taps must be "auto", a number or one per axis')
-            tp = list(blk.footprint_taps(footprint))
-        else:
-            try:
-                _, tp = blk.area_args(footprint, taps, self.dim_domain)
-            except ValueError as e:
-                raise ValueError(f"{who}: {e}") from None
-        return None if all(v == 1 for v in tp) else tp
-
     def sample_area(self, points, footprint, taps="auto", dtype=np.float32, quantized=False, want_mean=False, want_count=False,
                     to_host=True, blend=0.0):
         """Anti-aliased ``sample``, on the device (the engine's ``sample_area``; include/smoe_hip.h: smoe_sample_area): every
@@ -993,8 +994,8 @@ class Smoe(_SmoeBase):
         image are left out of the mean, so an edge cell stays as bright as an inside one; a cell with no tap inside gives 0.
         ``points``, ``dtype``, ``quantized``, ``blend`` and the kernel lists are ``sample``'s.  Returns ``[..., C]``; with
         ``want_mean`` also the float32 means before the lattice ``[..., C]``, with ``want_count`` the uint8 number of taps
-        inside ``[...]``.  ``to_host=False`` returns device tensors.  Several ranks: as ``sample``.  Per-block models only:
-        ``SharedSmoe`` has no counterpart."""
+        inside ``[...]``.  ``to_host=False`` returns device tensors.  Several ranks: as ``sample``.  The counterpart for a
+        whole-image model is ``SharedSmoe.eval_points_area``."""
         d = self.dim_domain
         bl = self._blend_arg("sample_area", blend)
         npdt = np.dtype(dtype)
@@ -1450,10 +1451,9 @@ class SharedSmoe(_SmoeBase):
         ids = None if ids is None else ids.reshape(lead)
         return self._eval_result((img, ids) if want_argmax else img, want_argmax, to_host)
 
-    def _view_tables(self, who, window, size, scale):
-        """``eval_view``'s window / size / scale, checked, as the engine's tables (numpy): per axis the coordinates and the
-        batch indices of the ``E_l`` samples (``blocks.view_axis``)."""
-        d, n = self.dim_domain, self.batch_size_valued
+    def _view_window(self, who, window, size, scale):
+        """``eval_view``'s window / size / scale, checked: one ``(lo, hi)`` per axis and the extent ``E``."""
+        d = self.dim_domain
         shape = [int(v) for v in self.image.shape[:d]]
         window = [None] * d if window is None else list(window)
         if len(window) != d:
@@ -1475,6 +1475,13 @@ class SharedSmoe(_SmoeBase):
             if len(sc) != d:
                 raise ValueError(f"{who}: scale needs one value or {d}")
             E = [max(1, int(round((hi - lo) * float(v)))) for (lo, hi), v in zip(win, sc)]
+        return win, E
+
+    def _view_tables(self, win, E):
+        """A checked window and extent (``_view_window``) as the engine's tables (numpy): per axis the coordinates and the
+        batch indices of the ``E_l`` samples (``blocks.view_axis``)."""
+        d, n = self.dim_domain, self.batch_size_valued
+        shape = [int(v) for v in self.image.shape[:d]]
         axes, batches = [], []
         for l in range(d):
             axes.append(blk.view_axis(shape[l], 1, shape[l], win[l][0], win[l][1], E[l])[3])
@@ -1483,7 +1490,7 @@ class SharedSmoe(_SmoeBase):
         return axes, batches
 
     def eval_view(self, window, size=None, scale=None, dtype=np.float32, quantized=False, want_argmax=False,
-                  to_host=True, use_lists=True):
+                  to_host=True, use_lists=True, taps=None):
         """Decode a viewport: the axis-aligned ``window`` of the image domain at the output ``size``, on the device (the
         engine's ``render_view``; include/smoe_hip.h: smoe_shared_render_view) -- ``Smoe.render_view`` for a whole-image
         model.  Only the window is computed and stored: an 8x detail, a fit-to-window zoom, a thumbnail with fewer samples
@@ -1493,19 +1500,70 @@ class SharedSmoe(_SmoeBase):
         scale_l))``; not both, neither: scale 1.  Sample ``i`` sits at ``lo + (i + 0.5)(hi - lo) / E_l``: its coordinate is
         ``blocks.view_axis(S, 1, S, lo, hi, E)[3]`` on the image axis of ``S`` pixels, its batch the one of
         ``blocks.view_axis(n, grid_l, S, lo, hi, E)`` -- a window that is a crop of a ``render`` grid gives exactly that
-        crop.  The other options and the return value are ``eval_points``'s, ``[*E, C]``."""
-        axes, batches = self._view_tables("eval_view", window, size, scale)
+        crop.  The other options and the return value are ``eval_points``'s, ``[*E, C]``.
+        ``taps``: None (the default) or all ones: one position per sample, as above.  Otherwise (a number, one per axis or
+        ``"auto"``) every sample is the mean over ``taps[l]`` taps per axis inside its cell -- ``eval_points_area`` at the
+        mesh of ``blocks.view_positions(lo, hi, E)`` with the footprint ``diag((hi - lo) / E)``: a thumbnail that does not
+        alias.  ``want_argmax`` is refused then (an average has no single kernel)."""
+        win, E = self._view_window("eval_view", window, size, scale)
+        foot = np.diag([(hi - lo) / e for (lo, hi), e in zip(win, E)])
+        tp = self._taps_arg("eval_view", taps, foot)
+        if tp is not None:
+            if want_argmax:
+                raise ValueError("eval_view: want_argmax needs taps=None (an average has no single kernel)")
+            axes = [blk.view_positions(lo, hi, e) for (lo, hi), e in zip(win, E)]     # view_axis' x_i, rounded once
+            pts = np.stack(np.meshgrid(*axes, indexing="ij"), axis=-1)
+            return self.eval_points_area(pts, foot, taps=tp, dtype=dtype, quantized=quantized, to_host=to_host,
+                                         use_lists=use_lists)
+        axes, batches = self._view_tables(win, E)
         tdt, eng, params, lists = self._eval_model("eval_view", dtype, quantized, use_lists, "render_view")
         axes, batches = ([torch.from_numpy(t).to(eng.device) for t in tabs] for tabs in (axes, batches))
         res = eng.render_view(params, lists, axes, batches, dtype=tdt, want_argmax=want_argmax)
         return self._eval_result(res, want_argmax, to_host)
 
-    def eval_warp(self, matrix, size, **options):
+    def eval_warp(self, matrix, size, taps=None, **options):
         """An affine view of the model: ``eval_points(blocks.warp_points(matrix, size), **options)`` -- ``Smoe.render_warp``
         for a whole-image model.  ``matrix = [M | t]`` ``[d, d + 1]`` maps the cell centre ``i + 0.5`` of output index ``i``
         to the source position ``M (i + 0.5) + t`` in source pixels.  Returns the image ``[*size, C]`` (0 where the view
-        leaves the image)."""
-        return self.eval_points(blk.warp_points(matrix, size), **options)
+        leaves the image).  ``taps``: None (the default) or all ones: that call.  Otherwise (a number, one per view axis or
+        ``"auto"``) ``eval_points_area`` at the same positions with the footprint ``M`` -- a zoomed-out warp that does not
+        alias; ``options`` are ``eval_points_area``'s then, and ``want_argmax`` is a ``ValueError``."""
+        pts = blk.warp_points(matrix, size)
+        M = np.asarray(matrix, dtype=np.float64)[:, :self.dim_domain]
+        tp = self._taps_arg("eval_warp", taps, M)
+        if tp is None:
+            return self.eval_points(pts, **options)
+        if options.pop("want_argmax", False):
+            raise ValueError("eval_warp: want_argmax needs taps=None (an average has no single kernel)")
+        return self.eval_points_area(pts, M, taps=tp, **options)
+
+    def eval_points_area(self, points, footprint, taps="auto", dtype=np.float32, quantized=False, want_mean=False,
+                         want_count=False, to_host=True, use_lists=True):
+        """Anti-aliased ``eval_points``, on the device (the engine's ``sample_area``; include/smoe_hip.h:
+        smoe_shared_sample_area) -- ``Smoe.sample_area`` for a whole-image model: every point is the centre of an output cell,
+        and its result is the mean of the model over a regular grid of taps inside the cell, put on the lattice.  Every tap
+        is evaluated with the kernel list of the batch IT lies in, so a cell that straddles batches is the mean of what
+        ``eval_points`` gives at its taps.  ``footprint`` ``[d, d]`` in source pixels: column ``m`` is the edge vector of a
+        cell along view axis ``m`` (``M`` of an affine view, ``diag((hi - lo) / E)`` of a viewport); one footprint serves all
+        points.  ``taps``: a number, one per view axis (1 .. 16, product at most 64) or ``"auto"``
+        (``blocks.footprint_taps``).  Positions: ``blocks.area_taps``.  Taps outside the image are left out of the mean; a
+        cell with no tap inside gives 0.  ``points``, ``dtype``, ``quantized``, ``use_lists`` and the lists are
+        ``eval_points``'s.  Returns ``[..., C]``; with ``want_mean`` also the float32 means before the lattice ``[..., C]``,
+        with ``want_count`` the uint8 number of taps inside ``[...]``.  ``to_host=False`` returns device tensors.  Several
+        ranks: as ``eval_points``."""
+        tdt, eng, params, lists = self._eval_model("eval_points_area", dtype, quantized, use_lists, "sample_area")
+        tp = self._taps_arg("eval_points_area", taps, footprint) or [1] * self.dim_domain
+        pts, lead = self._eval_points_arg("eval_points_area", points, eng.device)
+        res = eng.sample_area(params, lists, pts, footprint, tp, dtype=tdt, want_mean=want_mean, want_count=want_count)
+        res = list(res) if isinstance(res, tuple) else [res]
+        res[0] = res[0].reshape(lead + (self.channels,))
+        if want_mean:
+            res[1] = res[1].reshape(lead + (self.channels,))
+        if want_count:
+            res[-1] = res[-1].reshape(lead)
+        if to_host:
+            res = [t.cpu().numpy() for t in res]
+        return tuple(res) if len(res) > 1 else res[0]
 
     # -- the exact spatial derivative at the same points ----------------------------------------
     @staticmethod
@@ -1536,7 +1594,7 @@ class SharedSmoe(_SmoeBase):
         """The derivative on a viewport: ``eval_view``'s ``window`` / ``size`` / ``scale`` and sample positions (the engine's
         ``render_view_grad``; include/smoe_hip.h: smoe_shared_render_view_grad).  Returns ``[*E, d, C]`` per SOURCE pixel,
         with ``want_values`` also ``[*E, C]``; the other options are ``eval_points_grad``'s."""
-        axes, batches = self._view_tables("eval_view_grad", window, size, scale)
+        axes, batches = self._view_tables(*self._view_window("eval_view_grad", window, size, scale))
         _, eng, params, lists = self._eval_model("eval_view_grad", np.float32, quantized, use_lists, "render_view_grad")
         axes, batches = ([torch.from_numpy(t).to(eng.device) for t in tabs] for tabs in (axes, batches))
         res = eng.render_view_grad(params, lists, axes, batches, want_values=want_values)
