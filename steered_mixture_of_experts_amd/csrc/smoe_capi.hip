@@ -1164,6 +1164,12 @@ int smoe_sample_grad(smoe_handle h, const smoe_params* p, const uint32_t* active
     const int rp = render_plan(h, fn.c_str(), (int32_t)total, &v, &hl);
     if (rp != SMOE_OK) return rp;
     if (!v->sample_grad || !v->sample_grad_layout) return fail(SMOE_ERR_UNSUPPORTED, fn + ": no kernel variant for this handle");
+    // sample_grad_kernel<3, 3, 6, QUANT = false, IC = false, BLEND = true> is withheld (csrc/smoe_sample_grad.hip.h:
+    // sample_grad_kernel_for): on the MI355X it returned results that depend on the other points of the list
+    if (any && h->cfg.dim == 3 && h->cfg.channels == 3 && h->cfg.kernels == 6 && !h->kc.inverse_cov)
+        return fail(SMOE_ERR_UNSUPPORTED, fn + ": blend with dim 3, channels 3, kernels 6 and train_inverse_cov off is not served (the "
+                                               "kernel of this one instantiation is withheld, csrc/smoe_sample_grad.hip.h); use blend = 0, "
+                                               "train_inverse_cov, or another kernel count");
     smoe::SampleGradArgs a;
     std::memset(&a, 0, sizeof a);
     a.s = sample_args(h, total, *p, active, grid, length, points, num_points, blend, any, nullptr, SMOE_IMAGE_F32, nullptr, block);

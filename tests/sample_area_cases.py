@@ -12,8 +12,13 @@ LOOSE_CAP = 0.03        # of the covered points; the restatement alone gives at 
 
 
 def rotated_footprint(i):
-    """3 times the linear part of the case's warp on the first two axes, F[2][2] = 1.5; taps (3, 2) / (2, 2, 2)"""
-    shape, deg, zoom = CASES[i][0], CASES[i][5], CASES[i][6]
+    """the footprint and taps of case ``i``"""
+    return footprint_of(CASES[i][0], CASES[i][5], CASES[i][6])
+
+
+def footprint_of(shape, deg, zoom):
+    """3 times the linear part of the warp (``deg`` degrees, ``zoom``) on the first two axes, F[2][2] = 1.5; taps (3, 2) /
+    (2, 2, 2)"""
     d = len(shape)
     c, s = np.cos(np.deg2rad(deg)) / zoom, np.sin(np.deg2rad(deg)) / zoom
     F = np.zeros((d, d))

@@ -6,7 +6,7 @@ import pytest
 import torch
 
 from oracle import smoe_oracle as o
-from test_gpu_parity import SHAPES, _bits_to_mask, _close, _engine, _mask_to_bits, _planar, _setup, _to_dev, _to_host
+from test_gpu_parity import LATE_SHAPES, SHAPES, _bits_to_mask, _close, _engine, _mask_to_bits, _planar, _setup, _to_dev, _to_host
 
 pytestmark = pytest.mark.gpu
 
@@ -19,7 +19,12 @@ def _ic_setup(shape, C, kpd, yuv, B, seed, **kw):
     return cfg, p, coords, tgt, K
 
 
-@pytest.mark.parametrize("shape,C,kpd,yuv", SHAPES)
+# the FULL triples and the odd block shapes, then the triples no other deterministic case runs with train_inverse_cov (the basic
+# set of a triple that is not FULL holds the +ic kernels as well)
+IC_SHAPES = SHAPES + LATE_SHAPES
+
+
+@pytest.mark.parametrize("shape,C,kpd,yuv", IC_SHAPES)
 @pytest.mark.parametrize("tiling", [16, 64])
 def test_invcov_forward(shape, C, kpd, yuv, tiling):
     B = 29
@@ -50,7 +55,7 @@ def test_invcov_forward(shape, C, kpd, yuv, tiling):
     eng.close()
 
 
-@pytest.mark.parametrize("shape,C,kpd,yuv", SHAPES)
+@pytest.mark.parametrize("shape,C,kpd,yuv", IC_SHAPES)
 @pytest.mark.parametrize("tiling", [16, 64])
 def test_invcov_one_step_gradients(shape, C, kpd, yuv, tiling):
     B = 21

@@ -45,6 +45,19 @@ EXTRA_SHAPES = [
     ((8, 8, 8), 3, [2, 2, 2], True),
     ((16, 16, 4), 3, [1, 1, 1], True),
 ]
+# the triples of csrc/smoe_variants.def the lists above leave out: appended at the end, so that the slices below ([::3], [:6])
+# keep the entries they had (tests/test_triple_cases_cpu.py: SHAPES + EXTRA_SHAPES name every triple of the build)
+LATE_SHAPES = [
+    ((16, 16), 1, [1, 2], False),
+    ((16, 16), 1, [3, 1], False),
+    ((16, 16), 3, [1, 1], True),
+    ((8, 8, 4), 1, [1, 1, 1], False),
+    ((8, 8, 4), 1, [2, 1, 1], False),
+    ((8, 8, 4), 1, [3, 2, 1], False),
+    ((8, 8, 4), 3, [1, 2, 1], True),
+    ((8, 8, 4), 3, [3, 1, 1], True),
+]
+EXTRA_SHAPES = EXTRA_SHAPES + LATE_SHAPES
 ALL_SHAPES = [(s, 16) for s in SHAPES] + [(s, 64) for s in SHAPES] + [(s, 32) for s in SHAPES[:5]] \
     + [(s, 16) for s in EXTRA_SHAPES] + [(s, 64) for s in EXTRA_SHAPES]
 # 128 = one block on both wavefronts of a workgroup (smoe_fit only: the evaluation has no such mode)

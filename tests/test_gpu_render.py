@@ -138,6 +138,13 @@ def test_parity_on_resampled_grids(case):
     if kw.get("train_inverse_cov"):
         p["A_diagonal"] = (p["A_diagonal"] ** 2).astype(np.float32)
         p["A_corr"] = (p["A_corr"] * 2.0).astype(np.float32)
+    judge_resampled(shape, C_, yuv, m, kw, cfg, p, K, active, _grid_of(shape))
+
+
+def judge_resampled(shape, C_, yuv, m, kw, cfg, p, K, active, grid):
+    """the criterion of the module's docstring for the first ``len(active)`` blocks of ``grid`` rendered at ``m`` samples per
+    block: the condition on the inputs from the restatement alone, then the kernel"""
+    B = len(active)
     tabs = _axes(shape, m)
     ref, _ = oracle_blocks(p, active, tabs, cfg, np.float32)
     ref64, _ = oracle_blocks(p, active, tabs, cfg, np.float64)
@@ -156,14 +163,13 @@ def test_parity_on_resampled_grids(case):
     eng = _engine(shape, C_, K, use_yuv=yuv, **kw)
     dp = _to_dev(p)
     act = _bits(active)
-    grid = _grid_of(shape)
     extent = [g * mm for g, mm in zip(grid, m)]
     axes = _dev_axes(tabs)
     img = eng.render(dp, act, axes, grid, extent)
     u8 = eng.render(dp, act, axes, grid, extent, dtype=torch.uint8) if cfg.precision <= 8 else None     # (refused above 8 bits)
     torch.cuda.synchronize()
     img = img.cpu().numpy()
-    own = _owned(m, grid, extent, 0, B37)
+    own = _owned(m, grid, extent, 0, B)
     want = place_blocks(ref["recon"].astype(np.float32), m, grid, extent, 0, np.zeros(tuple(extent) + (C_,), np.float32))
     loose_img = place_blocks(np.broadcast_to(loose, tie.shape), m, grid, extent, 0, np.zeros(tuple(extent) + (C_,), bool))
     dd = np.abs(img - want)[own]

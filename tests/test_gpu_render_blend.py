@@ -75,7 +75,12 @@ def _inputs(i):
 def test_parity_with_the_restatement(i):
     shape, C_, kpd, m, beta, kw = CASES[i][:6]
     cfg, p, K, active, grid, tabs, ref, ref64 = _inputs(i)
-    B = int(np.prod(grid))
+    judge_blend(shape, C_, m, beta, kw, p, K, active, grid, tabs, ref, ref64)
+
+
+def judge_blend(shape, C_, m, beta, kw, p, K, active, grid, tabs, ref, ref64):
+    """the criterion of the module's docstring: the condition on the inputs from the restatement (``blend_reference`` in
+    float32 and float64) alone, then the kernel"""
     lsb = 1.0 / 255
     frac = (ref64["v"] * 255 + 0.5) % 1.0
     tie = (frac < 2e-4) | (frac > 1 - 2e-4)

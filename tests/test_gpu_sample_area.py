@@ -123,22 +123,23 @@ def test_taps_on_pixel_centres_are_the_ordered_sum_of_sample_grad(i, blended):
 # ---------------------------------------------------------------------------------------------------------------
 # 3. rotated footprints against the float64 restatement
 # ---------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("blended", [False, True], ids=["plain", "blend"])
-@pytest.mark.parametrize("i", range(len(CASES)), ids=CASE_IDS)
-def test_rotated_footprints_against_the_restatement(i, blended):
-    c = case_inputs(i, blended)
-    ref, ref64 = area_reference(i, blended)
-    F, taps = rotated_footprint(i)
+def rotated_conditions(ref, ref64):
+    """The condition on the inputs, asserted on the restatement alone: the counts of the two precisions agree, the loose share
+    of the covered points is at most LOOSE_CAP, no uncovered point is loose, and numpy's float32 differs from float64 on the
+    tight points.  Returns (covered, loose, tight, e32)."""
     covered = ref64["count"] > 0
     loose = loose_of(ref, ref64)
     assert np.array_equal(ref["count"], ref64["count"]) and loose[covered].mean() <= LOOSE_CAP and not loose[~covered].any()
     tight = covered & ~loose
     e32 = np.abs(ref["mean"].astype(np.float64) - ref64["mean"])[tight].max()
     assert e32 > 0
-    eng, dp, act, grid, _ = _open(tuple(c["shape"]), c["C"], c["kpd"], c["opt"])
-    img, mean, cnt, bk = (t.cpu().numpy() for t in _area(eng, dp, act, grid, c["length"], c["pts"], F, taps, blend=c["beta"]))
+    return covered, loose, tight, e32
+
+
+def judge_rotated(label, taps, ref64, covered, loose, tight, e32, img, mean, cnt, bk):
+    """the criterion of the module's docstring on the kernel's lattice image, mean, count and block ids (host arrays)"""
     dm = np.abs(mean - ref64["mean"])
-    print(f"{CASE_IDS[i]}-{'blend' if blended else 'plain'}: taps {'x'.join(map(str, taps))}, covered {covered.sum()} of {covered.size}, "
+    print(f"{label}: taps {'x'.join(map(str, taps))}, covered {covered.sum()} of {covered.size}, "
           f"partially {(covered & (ref64['count'] < ref64['inside'].shape[1])).sum()}, loose share of the covered {loose[covered].mean():.2e}, "
           f"near the floor of the normaliser {ref64['floor'].mean():.2e}; mean: e32 {e32:.2e}, kernel {dm[tight].max():.2e}, "
           f"ratio {dm[tight].max() / e32:.2f}; on the loose set {dm[loose].max() if loose.any() else 0:.2e}")
@@ -153,6 +154,18 @@ def test_rotated_footprints_against_the_restatement(i, blended):
     ok = ~tie & ~loose[:, None]
     assert (np.abs(img - want)[ok] < 1e-7).all(), np.abs(img - want)[ok].max()
     assert (np.abs(img - want) <= 1.0001 / 255)[~loose].all()
+
+
+@pytest.mark.parametrize("blended", [False, True], ids=["plain", "blend"])
+@pytest.mark.parametrize("i", range(len(CASES)), ids=CASE_IDS)
+def test_rotated_footprints_against_the_restatement(i, blended):
+    c = case_inputs(i, blended)
+    ref, ref64 = area_reference(i, blended)
+    F, taps = rotated_footprint(i)
+    covered, loose, tight, e32 = rotated_conditions(ref, ref64)
+    eng, dp, act, grid, _ = _open(tuple(c["shape"]), c["C"], c["kpd"], c["opt"])
+    img, mean, cnt, bk = (t.cpu().numpy() for t in _area(eng, dp, act, grid, c["length"], c["pts"], F, taps, blend=c["beta"]))
+    judge_rotated(f"{CASE_IDS[i]}-{'blend' if blended else 'plain'}", taps, ref64, covered, loose, tight, e32, img, mean, cnt, bk)
     eng.close()
 
 

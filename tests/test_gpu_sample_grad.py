@@ -108,28 +108,26 @@ def test_points_outside_every_band_have_the_bits_of_the_plain_call(i):
 # ---------------------------------------------------------------------------------------------------------------
 # 3. / 4. rotated point sets against the restatement; consistency with smoe_sample
 # ---------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("blended", [False, True], ids=["plain", "blend"])
-@pytest.mark.parametrize("i", range(len(CASES)), ids=CASE_IDS)
-def test_rotated_points_against_the_restatement(i, blended):
-    c = case_inputs(i, blended)
-    ref, ref64 = case_reference(i, blended)
-    shape, C_ = c["shape"], c["C"]
+def rotated_conditions(ref, ref64, n_out, npts):
+    """The condition on the inputs, asserted on the restatement alone: the blocks of the two precisions agree, ``n_out`` points
+    lie outside, loose share < 0.01, and numpy's float32 differs from float64 outside the loose set.  Returns (loose, outside,
+    eJ, eV)."""
     outside = ref64["block"] < 0
     loose = ref64["loose"]
-    assert outside.sum() == c["n_out"] and np.array_equal(ref64["block"], ref["block"])
+    assert outside.sum() == n_out and np.array_equal(ref64["block"], ref["block"])
     print(f"restatement: loose share {loose.mean():.2e}, near the floor of the normaliser {ref64['floor'].mean():.2e}, "
-          f"outside {outside.sum()} of {len(c['pts'])}")
+          f"outside {outside.sum()} of {npts}")
     assert loose.mean() < 0.01
     eJ = np.abs(ref["jac"].astype(np.float64) - ref64["jac"])[~loose].max()
     eV = np.abs(ref["v"].astype(np.float64) - ref64["v"])[~loose].max()
     assert eJ > 0 and eV > 0
+    return loose, outside, eJ, eV
 
-    eng, dp, act, grid, _ = _open(tuple(shape), C_, c["kpd"], c["opt"])
-    jac, val, bk = _grad(eng, dp, act, grid, shape, c["pts"], blend=c["beta"])
-    img = eng.sample(dp, act, grid, c["length"], _dev(c["pts"]), blend=c["beta"])
-    torch.cuda.synchronize()
-    jac, val, bk, img = jac.cpu().numpy(), val.cpu().numpy(), bk.cpu().numpy(), img.cpu().numpy()
-    assert jac.shape == (len(c["pts"]), len(shape), C_) and val.shape == (len(c["pts"]), C_)
+
+def judge_rotated(ref64, loose, outside, eJ, eV, jac, val, bk, img):
+    """the criterion of the module's docstring on the kernel's Jacobian, values and block ids, and the values against
+    smoe_sample's image ``img`` (host arrays)"""
+    assert jac.shape == ref64["jac"].shape and val.shape == ref64["v"].shape
     dJ, dV = np.abs(jac - ref64["jac"]), np.abs(val - ref64["v"])
     print(f"kernel: max |J| {np.abs(ref64['jac']).max():.3f} per pixel; J: e32 {eJ:.2e}, kernel {dJ[~loose].max():.2e}, ratio "
           f"{dJ[~loose].max() / eJ:.2f}; values: e32 {eV:.2e}, kernel {dV[~loose].max():.2e}, ratio {dV[~loose].max() / eV:.2f}; "
@@ -147,6 +145,23 @@ def test_rotated_points_against_the_restatement(i, blended):
     print(f"against smoe_sample: tie share {tie.mean():.2e}, samples that differ {(dd > 1e-7).mean():.2e}")
     assert (dd[~tie] < 1e-7).all(), dd[~tie].max()
     assert (dd <= lsb * 1.0001).all(), dd.max()
+
+
+@pytest.mark.parametrize("blended", [False, True], ids=["plain", "blend"])
+@pytest.mark.parametrize("i", range(len(CASES)), ids=CASE_IDS)
+def test_rotated_points_against_the_restatement(i, blended):
+    c = case_inputs(i, blended)
+    ref, ref64 = case_reference(i, blended)
+    shape, C_ = c["shape"], c["C"]
+    loose, outside, eJ, eV = rotated_conditions(ref, ref64, c["n_out"], len(c["pts"]))
+
+    eng, dp, act, grid, _ = _open(tuple(shape), C_, c["kpd"], c["opt"])
+    jac, val, bk = _grad(eng, dp, act, grid, shape, c["pts"], blend=c["beta"])
+    img = eng.sample(dp, act, grid, c["length"], _dev(c["pts"]), blend=c["beta"])
+    torch.cuda.synchronize()
+    jac, val, bk, img = jac.cpu().numpy(), val.cpu().numpy(), bk.cpu().numpy(), img.cpu().numpy()
+    assert jac.shape == (len(c["pts"]), len(shape), C_) and val.shape == (len(c["pts"]), C_)
+    judge_rotated(ref64, loose, outside, eJ, eV, jac, val, bk, img)
     eng.close()
 
 
