@@ -385,7 +385,7 @@ int smoe_sample_grad(smoe_handle h, const smoe_params* p, const uint32_t* active
  *                            thumbnail stays as bright as its inside
  * No argmax: an average has no single kernel.  The result for a point depends on its coordinates, footprint, taps and the
  * model only: not on num_points, its place in the list, the other points, staging or how the launch is cut.
- * Limits: one footprint per call (an affine view); at most 64 taps (an 8 x 8 box: a 1/8 thumbnail; 4 x 4 x 4: video);
+ * Limits: one footprint per call (an affine view; smoe_sample_area_each takes one per point); at most 64 taps (an 8 x 8 box: a 1/8 thumbnail; 4 x 4 x 4: video);
  * per-block models only -- the counterpart for the whole-image models of smoe_shared_sample is smoe_shared_sample_area.
  * A workgroup takes 256 consecutive points and bounds the blocks of all their taps: the centres' box widened per axis by the
  * footprint's half extent 0.5 sum_m |F[l][m]| plus one block (with blend: one more); records are staged as in smoe_sample where
@@ -399,6 +399,39 @@ int smoe_sample_area(smoe_handle h, const smoe_params* p, const uint32_t* active
                      const int32_t length[3], const float* points, int64_t num_points, const float* footprint,
                      const int32_t* taps, const float blend[3], void* values, int32_t image_format, float* mean,
                      uint8_t* count, int32_t* block, void* stream);
+
+/* smoe_sample_area with a footprint and tap counts of its own for every point: a view whose magnification varies across the
+ * output -- a perspective view (a homography), a lens-distortion or stabilisation map, a fisheye or polar unwrapping, any dense
+ * lookup map.  One fused kernel; nothing is materialised per tap.
+ *   points, grid, length, p, active, blend, values, image_format, mean, count, block     smoe_sample_area's, with its outside
+ *                            rule, its lattice, "a centre outside with taps inside still gets their mean", block = the centre's
+ *                            own block, and no argmax
+ *   footprints               DEVICE [num_points, dim, dim] fp32, row-major per point, source pixels; any 4-byte address
+ *   taps                     DEVICE [num_points, dim] uint8; any address
+ * For point i with F = footprints[i], n = taps[i] and tap multi-index j (0 <= j_m < n_m) the arithmetic is smoe_sample_area's
+ * statement word for word, in IEEE fp32: o_m = (float)(2 j_m + 1 - n_m) / (float)(2 n_m); t_l = x_l, then for m = 0 .. dim-1
+ * t_l = t_l + (F[l][m] * o_m), product and sum rounded separately (blocks.area_taps_each gives the positions bit for bit); taps
+ * walked in row-major order of j; an inside tap adds acc_c = acc_c + V_c and cnt += 1; mean_c = acc_c / (float)cnt.  The result
+ * for point i is therefore bit for bit the result of smoe_sample_area called with that one point, that footprint and those taps.
+ * VOID points: a point is void if any taps[i][m] is outside 1 .. 16, if prod(taps[i]) > 64, or if any entry of footprints[i] is
+ * not finite.  A void point gives values 0, mean 0 and count 0; its block is still the centre's own block; it never affects
+ * another point.  The host cannot check device arrays, so this is a defined result and there is no error code for it; whatever
+ * bytes the arrays hold, the kernel indexes inside its tables and no point takes more than 64 taps.
+ * A workgroup takes 256 consecutive points.  The box of blocks it stages bounds every point's taps by the point's own half
+ * extents 0.5 sum_m |F[l][m]| (computed in the kernel, not rounded up exactly: a tap whose block falls outside the box is
+ * derived directly and gives the same bits, so the box is a performance device only); void points add nothing to it; one point
+ * with a huge footprint -- |F| reaches thousands of pixels near a horizon -- sends its workgroup onto the unstaged path, with
+ * the same bits (SMOE_SAMPLE_RECORDS applies).  Lanes run their own trip counts; points are never sorted or re-binned.
+ * footprints and taps are loaded 16 / 4 bytes wide where their base is aligned so, element-wise otherwise: the same bits.
+ * Limits: the equal-weight box filter, at most 16 taps per axis and 64 per point, per-block models only (there is no
+ * smoe_shared_sample_area_each).
+ * num_points == 0 is a successful no-op.  SMOE_ERR_INVALID names the offending argument: smoe_sample_area's cases (its host
+ * footprint / taps checks excepted), plus (num_points > 0) a null footprints or taps.  SMOE_ERR_UNSUPPORTED: as
+ * smoe_sample_area. */
+int smoe_sample_area_each(smoe_handle h, const smoe_params* p, const uint32_t* active, const int32_t grid[3],
+                          const int32_t length[3], const float* points, int64_t num_points, const float* footprints,
+                          const uint8_t* taps, const float blend[3], void* values, int32_t image_format, float* mean,
+                          uint8_t* count, int32_t* block, void* stream);
 
 /* Name of the kernel variant smoe_fit would launch for num_blocks (diagnostics / profiles). */
 const char* smoe_fit_variant(smoe_handle h, int32_t num_blocks);

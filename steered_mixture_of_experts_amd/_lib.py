@@ -33,6 +33,7 @@ EXPORTS = (
     "smoe_render", "smoe_shared_render", "smoe_last_fit_variant", "smoe_render_blend",
     "smoe_render_view", "smoe_sample", "smoe_shared_sample", "smoe_shared_render_view", "smoe_sample_grad",
     "smoe_shared_sample_grad", "smoe_shared_render_view_grad", "smoe_sample_area", "smoe_shared_sample_area",
+    "smoe_sample_area_each",
 )
 
 
@@ -122,6 +123,8 @@ def load() -> C.CDLL:
                                      C.POINTER(C.c_float), fp, fp, fp, vp]
     lib.smoe_sample_area.argtypes = [vp, C.POINTER(SmoeParams), fp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), fp, C.c_int64,
                                      C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_float), fp, i32, fp, fp, fp, vp]
+    lib.smoe_sample_area_each.argtypes = [vp, C.POINTER(SmoeParams), fp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), fp,
+                                          C.c_int64, fp, fp, C.POINTER(C.c_float), fp, i32, fp, fp, fp, vp]
     lib.smoe_fit_variant.argtypes = [vp, i32]
     lib.smoe_fit_variant.restype = C.c_char_p
     lib.smoe_last_fit_variant.argtypes = [vp]

@@ -264,6 +264,126 @@ def footprint_taps(footprint):
     return tuple(tp)
 
 
+def area_void_each(footprints, taps) -> np.ndarray:
+    """The void rule of smoe_sample_area_each (include/smoe_hip.h) for ``footprints`` ``[N, d, d]`` and ``taps`` ``[N, d]``:
+    a point is void if a tap count is outside 1 .. 16, if the counts multiply to more than 64 or if an entry of its footprint
+    is not finite.  Returns bool ``[N]``."""
+    F = np.asarray(footprints, dtype=np.float32)
+    tp = np.asarray(taps).astype(np.int64)
+    return (tp < 1).any(axis=1) | (tp > AREA_AXIS_TAPS).any(axis=1) | (np.prod(np.clip(tp, 0, 255), axis=1) > AREA_TAPS) \
+        | ~np.isfinite(F).all(axis=(1, 2))
+
+
+def area_taps_each(points, footprints, taps):
+    """The tap positions of area-averaged samples with a footprint of their own per point (``Smoe.sample_area_each``,
+    include/smoe_hip.h: smoe_sample_area_each) -- the one host statement of the arithmetic: ``area_taps`` per point, in float32
+    throughout.  ``points`` ``[N, d]``, ``footprints`` ``[N, d, d]``, ``taps`` ``[N, d]`` integers.  Slot ``t`` of point ``i``
+    is its tap with the row-major index ``t`` under ITS counts (last axis fastest): offset ``o_m = float32(2 j_m + 1 - n_m) /
+    float32(2 n_m)``, position ``t_l = x_l``, then for ``m = 0 .. d-1`` ``t_l = t_l + (F[l][m] * o_m)``, product and sum rounded
+    separately.  Returns ``(positions float32 [N, 64, d], valid bool [N, 64])``: a slot past ``prod(taps[i])`` and every slot
+    of a void point (``area_void_each``) is not valid and holds NaN."""
+    pts = np.asarray(points, dtype=np.float32)
+    if pts.ndim != 2:
+        raise ValueError("area_taps_each: points must be [N, d]")
+    N, d = pts.shape
+    F = np.asarray(footprints, dtype=np.float32)
+    tp = np.asarray(taps)
+    if F.shape != (N, d, d) or tp.shape != (N, d) or tp.dtype.kind not in "iu":
+        raise ValueError(f"area_taps_each: footprints must be [{N}, {d}, {d}] and taps integers [{N}, {d}]")
+    void = area_void_each(F, tp)
+    n = np.where(void[:, None], 1, tp.astype(np.int64))                                  # [N, d]
+    t = np.arange(AREA_TAPS, dtype=np.int64)[None, :]                                    # [1, 64]
+    valid = (t < np.prod(n, axis=1)[:, None]) & ~void[:, None]
+    j = np.empty((N, AREA_TAPS, d), dtype=np.int64)
+    r = np.broadcast_to(t, (N, AREA_TAPS)).copy()
+    for m in range(d - 1, -1, -1):
+        j[:, :, m] = r % n[:, None, m]
+        r //= n[:, None, m]
+    off = (2 * j + 1 - n[:, None, :]).astype(np.float32) / (2 * n[:, None, :]).astype(np.float32)      # [N, 64, d]
+    out = np.empty((N, AREA_TAPS, d), dtype=np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for l in range(d):
+            v = np.repeat(pts[:, l:l + 1], AREA_TAPS, axis=1)
+            for m in range(d):
+                v = (v + (F[:, None, l, m] * off[:, :, m]).astype(np.float32)).astype(np.float32)
+            out[:, :, l] = v
+    out[~valid] = np.float32("nan")
+    return out, valid
+
+
+def footprint_taps_each(footprints) -> np.ndarray:
+    """``taps="auto"`` of ``Smoe.sample_area_each``: ``footprint_taps``' rule per point, evaluated on the float32 entries --
+    ``n_m = clamp(ceil(max_l |F[l][m]|), 1, 16)``, then the largest entry (the first of equals) is decremented until the
+    product is at most 64.  A footprint with a non-finite entry gets taps 0, which marks the point void.  ``footprints``
+    ``[N, d, d]``; returns uint8 ``[N, d]``."""
+    F = np.asarray(footprints, dtype=np.float32)
+    if F.ndim != 3 or F.shape[1] != F.shape[2]:
+        raise ValueError("footprint_taps_each: footprints must be [N, d, d]")
+    fin = np.isfinite(F).all(axis=(1, 2))
+    with np.errstate(invalid="ignore"):
+        tp = np.clip(np.ceil(np.abs(np.where(fin[:, None, None], F, np.float32(0))).max(axis=1)), 1, AREA_AXIS_TAPS).astype(np.int64)
+    rows = np.arange(F.shape[0])
+    while True:
+        over = np.prod(tp, axis=1) > AREA_TAPS
+        if not over.any():
+            break
+        tp[rows[over], np.argmax(tp[over], axis=1)] -= 1
+    tp[~fin] = 0
+    return tp.astype(np.uint8)
+
+
+def projective_points(H, size: Sequence[int]):
+    """The source positions and footprints of a projective view (``Smoe.render_projective``): ``H`` ``[d + 1, d + 1]`` maps the
+    cell centre ``c = i + 0.5`` of output index ``i`` to ``x = (H[:d, :d] c + H[:d, d]) / s`` with ``s = H[d, :d] . c + H[d, d]``,
+    in source pixels; the footprint is the analytic Jacobian ``J[l][m] = (H[l][m] - x_l H[d][m]) / s``.  Computed in float64,
+    rounded to float32 once.  Where ``s <= 0`` or ``s`` is not finite the sample is behind the horizon: ``valid`` False, the
+    point NaN, the footprint 0.  With the last row ``(0, .., 0, 1)`` the points are ``warp_points([M | t], size)`` and every
+    footprint is ``float32(M)``, bit for bit.  Returns ``(points float32 [*size, d], footprints float32 [*size, d, d], valid
+    bool [*size])``."""
+    size = [int(v) for v in np.atleast_1d(size)]
+    d = len(size)
+    Hm = np.asarray(H, dtype=np.float64)
+    if Hm.shape != (d + 1, d + 1) or not np.isfinite(Hm).all():
+        raise ValueError(f"projective_points: H must be a finite [{d + 1}, {d + 1}] array")
+    if min(size) < 1:
+        raise ValueError("projective_points: size needs entries >= 1")
+    idx = np.stack(np.meshgrid(*[np.arange(e, dtype=np.float64) + 0.5 for e in size], indexing="ij"), axis=-1)
+    with np.errstate(all="ignore"):
+        s = idx @ Hm[d, :d] + Hm[d, d]
+        valid = np.isfinite(s) & (s > 0)
+        sv = np.where(valid, s, 1.0)
+        A = Hm[:d]                                                                     # (warp_points' expression on [M | t])
+        x = (idx @ A[:, :d].T + A[:, d]) / sv[..., None]
+        J = (Hm[:d, :d] - x[..., :, None] * Hm[d, :d]) / sv[..., None, None]
+    pts = np.where(valid[..., None], x, np.nan).astype(np.float32)
+    foot = np.where(valid[..., None, None], J, 0.0).astype(np.float32)
+    return pts, foot, valid
+
+
+def map_footprints(points) -> np.ndarray:
+    """The footprints of a dense lookup map (``Smoe.render_map``): ``points`` ``[*size, d]`` holds the source position of every
+    output sample; column ``m`` of a sample's footprint is the central difference ``(p[i + e_m] - p[i - e_m]) * 0.5`` in
+    float32, one-sided (``p[i + e_m] - p[i]`` / ``p[i] - p[i - e_m]``) at the ends of an axis and 0 on an axis of one sample.  A
+    NaN neighbour makes the footprint non-finite, hence the sample void.  Returns float32 ``[*size, d, d]``."""
+    p = np.asarray(points, dtype=np.float32)
+    d = p.shape[-1] if p.ndim >= 1 else 0
+    if p.ndim != d + 1 or d < 1:
+        raise ValueError("map_footprints: points must be [*size, d] with d view axes")
+    F = np.zeros(p.shape + (d,), dtype=np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for m in range(d):
+            E = p.shape[m]
+            if E < 2:
+                continue
+            q = np.moveaxis(p, m, 0)
+            col = np.empty_like(q)
+            col[1:-1] = ((q[2:] - q[:-2]).astype(np.float32) * np.float32(0.5)).astype(np.float32)
+            col[0] = q[1] - q[0]
+            col[-1] = q[-1] - q[-2]
+            F[..., m] = np.moveaxis(col, 0, m)
+    return F
+
+
 def to_planar(blocks: np.ndarray) -> np.ndarray:
     """(B, *block_shape, C) -> (B, C, N): the C-ABI target layout (include/smoe_hip.h)."""
     B, C = blocks.shape[0], blocks.shape[-1]

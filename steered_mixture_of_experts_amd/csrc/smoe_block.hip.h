@@ -2658,7 +2658,8 @@ int fit_occupancy(int N, bool has_lw, int hoist, bool pair) {
       &render_view_layout<D, C, K, (SMOE_FULL != 0)>, &launch_render_view<D, C, K, (SMOE_FULL != 0)>, \
       &sample_layout<D, C, K, (SMOE_FULL != 0)>, &launch_sample<D, C, K, (SMOE_FULL != 0)>, \
       &sample_grad_layout<D, C, K, (SMOE_FULL != 0)>, &launch_sample_grad<D, C, K, (SMOE_FULL != 0)>, \
-      &sample_area_layout<D, C, K, (SMOE_FULL != 0)>, &launch_sample_area<D, C, K, (SMOE_FULL != 0)> }
+      &sample_area_layout<D, C, K, (SMOE_FULL != 0)>, &launch_sample_area<D, C, K, (SMOE_FULL != 0)>, \
+      &sample_area_each_layout<D, C, K, (SMOE_FULL != 0)>, &launch_sample_area_each<D, C, K, (SMOE_FULL != 0)> }
 
 }  // namespace smoe
 #endif

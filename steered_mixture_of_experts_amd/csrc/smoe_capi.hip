@@ -1266,6 +1266,59 @@ int smoe_sample_area(smoe_handle h, const smoe_params* p, const uint32_t* active
 #endif
 }
 
+int smoe_sample_area_each(smoe_handle h, const smoe_params* p, const uint32_t* active, const int32_t grid[3],
+                          const int32_t length[3], const float* points, int64_t num_points, const float* footprints,
+                          const uint8_t* taps, const float blend[3], void* values, int32_t image_format, float* mean,
+                          uint8_t* count, int32_t* block, void* stream) {
+    const std::string fn = "smoe_sample_area_each";
+    if (!h) return fail(SMOE_ERR_INVALID, fn + ": null handle");
+    if (!params_ok(p)) return fail(SMOE_ERR_INVALID, fn + ": p (all six parameter tensors) is required");
+    if (!grid) return fail(SMOE_ERR_INVALID, fn + ": grid is required");
+    if (!length) return fail(SMOE_ERR_INVALID, fn + ": length is required");
+    if (image_format != SMOE_IMAGE_F32 && image_format != SMOE_IMAGE_U8)
+        return fail(SMOE_ERR_INVALID, fn + ": image_format must be SMOE_IMAGE_F32 or SMOE_IMAGE_U8");
+    if (num_points < 0) return fail(SMOE_ERR_INVALID, fn + ": num_points must be >= 0");
+    long long total = 1;
+    bool exact = true, any = false;
+    int rc = point_grid_check(h, fn, grid, length, &total, &exact);
+    if (rc == SMOE_OK) rc = blend_check(h, fn, blend, &any);
+    if (rc != SMOE_OK) return rc;
+    if (num_points == 0) return SMOE_OK;
+    if (!points) return fail(SMOE_ERR_INVALID, fn + ": points is required");
+    if (!footprints) return fail(SMOE_ERR_INVALID, fn + ": footprints is required");
+    if (!taps) return fail(SMOE_ERR_INVALID, fn + ": taps is required");
+    if (!values && !mean) return fail(SMOE_ERR_INVALID, fn + ": values or mean is required");
+    if (!exact) return fail(SMOE_ERR_UNSUPPORTED, fn + ": grid * block_shape must not exceed 2^24 on any axis (block origins are exact in fp32)");
+    if (values && image_format == SMOE_IMAGE_U8 && h->cfg.precision > 8)
+        return fail(SMOE_ERR_UNSUPPORTED, fn + ": SMOE_IMAGE_U8 needs precision <= 8");
+
+    // the kernel lists, the fake quantisation and the centre grid of a decode of the whole image: the variant of prod(grid) blocks
+    const smoe::Variant* v = nullptr;
+    int hl = 0;
+    const int rp = render_plan(h, fn.c_str(), (int32_t)total, &v, &hl);
+    if (rp != SMOE_OK) return rp;
+    if (!v->sample_area_each || !v->sample_area_each_layout) return fail(SMOE_ERR_UNSUPPORTED, fn + ": no kernel variant for this handle");
+    smoe::SampleAreaEachArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.s = sample_args(h, total, *p, active, grid, length, points, num_points, blend, any, values, image_format, nullptr, block);
+    a.footprints = footprints; a.taps = taps;
+    a.mean = mean; a.count = count;
+    a.vec_mean = ((uintptr_t)mean % 16 == 0) ? 1 : 0;
+    a.vec_cnt = ((uintptr_t)count % 16 == 0) ? 1 : 0;
+    a.vec_fp = ((uintptr_t)footprints % 16 == 0) ? 1 : 0;
+    a.vec_tap = ((uintptr_t)taps % 4 == 0) ? 1 : 0;
+    smoe::RenderLayout lay;
+    const char* const unsupported = "the launch would need 2^31 or more workgroups or more than 160 KB of LDS (or the graph variant is not built for the triple)";
+    rc = decoder_launched(fn, v->sample_area_each_layout(a, sample_records(), lay), unsupported);
+    if (rc != SMOE_OK) return rc;
+#if !SMOE_HOST_TEST
+    return decoder_launched(fn, v->sample_area_each(a, lay, (hipStream_t)stream), unsupported);
+#else
+    (void)stream;
+    return SMOE_OK;
+#endif
+}
+
 int smoe_update_kernel_list(smoe_handle h, int32_t num_blocks, const smoe_params* p,
                             uint32_t* active, void* stream) {
     if (!h) return fail(SMOE_ERR_INVALID, "smoe_update_kernel_list: null handle");

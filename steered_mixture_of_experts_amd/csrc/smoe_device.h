@@ -231,6 +231,20 @@ struct SampleAreaArgs {
     int off_tap;              // float offset of the tap table in the dynamic LDS (launcher)
 };
 
+// smoe_sample_area_each (smoe_sample_area_each.hip.h): smoe_sample_area with a footprint and tap counts of its own for every
+// point.  s, mean, count as in SampleAreaArgs.
+struct SampleAreaEachArgs {
+    SampleArgs s;
+    const float* footprints;  // [N, dim, dim] row-major per point, source pixels
+    const uint8_t* taps;      // [N, dim] taps per view axis
+    float* mean;              // [N, C] the mean before the lattice, or null
+    uint8_t* count;           // [N] taps inside the image, or null
+    int vec_mean, vec_cnt;    // the plane's base is 16-byte aligned: vector stores
+    int vec_fp, vec_tap;      // footprints' base is 16-byte aligned / taps' base is 4-byte aligned: wide loads
+    int off_tab;              // float offset of the offset table o[n][j] in the dynamic LDS (launcher)
+    int off_fp, off_tap;      // float offsets of the workgroup's footprints and tap counts in the dynamic LDS (launcher)
+};
+
 // What the launcher of a block decoder derives from checked arguments, next to the geometry fields of RenderArgs (and off_w
 // of RenderBlendArgs) it fills: a pure host computation (render_layout / render_blend_layout), also run without a device
 struct RenderLayout {
@@ -287,6 +301,9 @@ struct Variant {
     // area-averaged point decoder (smoe_sample_area.hip.h), same conventions
     hipError_t (*sample_area_layout)(SampleAreaArgs&, long long records, RenderLayout&);
     hipError_t (*sample_area)(const SampleAreaArgs&, const RenderLayout&, hipStream_t);
+    // area-averaged point decoder with per-point footprints (smoe_sample_area_each.hip.h), same conventions
+    hipError_t (*sample_area_each_layout)(SampleAreaEachArgs&, long long records, RenderLayout&);
+    hipError_t (*sample_area_each)(const SampleAreaEachArgs&, const RenderLayout&, hipStream_t);
 };
 
 // ---- shared-kernel image mode (smoe_shared.hip) ----------------------------------------------

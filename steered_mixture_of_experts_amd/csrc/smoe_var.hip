@@ -9,6 +9,7 @@
 #include "smoe_sample.hip.h"
 #include "smoe_sample_grad.hip.h"
 #include "smoe_sample_area.hip.h"
+#include "smoe_sample_area_each.hip.h"
 
 #if !defined(SMOE_D) || !defined(SMOE_C) || !defined(SMOE_K) || !defined(SMOE_FULL)
 #error "compile with -DSMOE_D -DSMOE_C -DSMOE_K -DSMOE_FULL (see csrc/Makefile)"

@@ -534,6 +534,40 @@ class BlockEngine(_Engine):
         res = (out,) + ((mean,) if want_mean else ()) + ((cnt,) if want_count else ()) + ((bk,) if want_block else ())
         return res if len(res) > 1 else out
 
+    def sample_area_each(self, params, active, grid, length, points, footprints, taps, blend=None, out=None, dtype=torch.float32,
+                         want_mean=False, want_count=False, want_block=False, center_grid=None):
+        """Anti-aliased point decode with a footprint of its own per point (include/smoe_hip.h: smoe_sample_area_each):
+        ``sample_area`` where point ``i`` has the footprint ``footprints[i]`` and the tap counts ``taps[i]`` -- contiguous
+        device tensors, float32 ``[N, d, d]`` and uint8 ``[N, d]`` (``blocks.area_taps_each`` states the positions).  A point
+        whose taps are outside 1 .. 16, multiply to more than 64 or whose footprint is not finite is void: 0 / 0 / count 0.
+        Everything else, and what is returned, is ``sample_area``'s."""
+        who = "sample_area_each"
+        grid, length = [int(g) for g in grid], [int(v) for v in length]
+        if dtype not in (torch.float32, torch.uint8):
+            raise ValueError(f"{who}: dtype must be torch.float32 or torch.uint8")
+        N, bl = self._check_point_args(who, params, active, grid, length, points, blend)
+        d = self.cfg.dim
+        if not torch.is_tensor(footprints) or tuple(footprints.shape) != (N, d, d) or footprints.dtype != torch.float32 \
+                or not footprints.is_contiguous() or footprints.device != self.device:
+            raise ValueError(f"{who}: footprints must be a contiguous float32 tensor [{N}, {d}, {d}] on {self.device}")
+        if not torch.is_tensor(taps) or tuple(taps.shape) != (N, d) or taps.dtype != torch.uint8 or not taps.is_contiguous() \
+                or taps.device != self.device:
+            raise ValueError(f"{who}: taps must be a contiguous uint8 tensor [{N}, {d}] on {self.device}")
+        out = self._point_out(who, out, (N, self.cfg.channels), dtype, dtype)
+        fmt = _lib.SMOE_IMAGE_U8 if dtype == torch.uint8 else _lib.SMOE_IMAGE_F32
+        mean = torch.empty((N, self.cfg.channels), dtype=torch.float32, device=self.device) if want_mean else None
+        cnt = torch.empty((N,), dtype=torch.uint8, device=self.device) if want_count else None
+        bk = torch.empty((N,), dtype=torch.int32, device=self.device) if want_block else None
+        cp = self._cparams(params)
+        with self._center_grid_installed(center_grid):
+            rc = self.lib.smoe_sample_area_each(self._h, C.byref(cp), _ptr(active), _slots(C.c_int32, grid, 1),
+                                                _slots(C.c_int32, length, 1), _ptr(points), N, _ptr(footprints), _ptr(taps),
+                                                None if bl is None else _slots(C.c_float, bl, 0.0), _ptr(out), fmt, _ptr(mean),
+                                                _ptr(cnt), _ptr(bk), self._stream())
+        _lib.check(rc)
+        res = (out,) + ((mean,) if want_mean else ()) + ((cnt,) if want_count else ()) + ((bk,) if want_block else ())
+        return res if len(res) > 1 else out
+
     def fit(self, target, params, state: AdamState, active, n_iters: int, loss_w=None, diverged=None,
             loss0=None, loss_out=None, sse_out=None, loss_w_is_sample=False):
         """loss_w_is_sample: ``loss_w`` is a pixel sub-sample (N / n for the drawn pixels, 0 otherwise; smoe.py:1664-1667):

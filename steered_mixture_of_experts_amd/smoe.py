@@ -103,6 +103,39 @@ def _warp_chain(jac: torch.Tensor, matrix, d: int) -> torch.Tensor:
     return torch.einsum("...lc,lm->...mc", jac, M).contiguous()
 
 
+def footprint_taps_each_torch(foot: torch.Tensor) -> torch.Tensor:
+    """``blocks.footprint_taps_each`` on the device of ``foot`` (float32 ``[N, d, d]``): the same integers -- ceil, max and the
+    comparisons are exact in float32 --, uint8 ``[N, d]``."""
+    fin = torch.isfinite(foot).all(dim=2).all(dim=1)
+    a = torch.where(fin[:, None, None], foot, torch.zeros_like(foot)).abs().amax(dim=1)
+    tp = torch.ceil(a).clamp(1, blk.AREA_AXIS_TAPS).to(torch.int64)
+    # a fixed number of masked rounds, no read-back: from (16, .., 16) the product is at most 64 after d * 15 decrements at the
+    # latest (every count at 1), and a round changes nothing once it is
+    for _ in range(tp.shape[1] * (blk.AREA_AXIS_TAPS - 1)):
+        over = tp.prod(dim=1) > blk.AREA_TAPS
+        ismax = tp == tp.amax(dim=1, keepdim=True)
+        first = ismax & (ismax.to(torch.int64).cumsum(dim=1) == 1)                       # the first of equals
+        tp = tp - (first & over[:, None]).to(torch.int64)
+    return torch.where(fin[:, None], tp, torch.zeros_like(tp)).to(torch.uint8).contiguous()
+
+
+def map_footprints_torch(p: torch.Tensor) -> torch.Tensor:
+    """``blocks.map_footprints`` on the device of ``p`` (float32 ``[*size, d]``): the same float32 differences,
+    ``[*size, d, d]``."""
+    d = p.shape[-1]
+    F = torch.zeros(tuple(p.shape) + (d,), dtype=torch.float32, device=p.device)
+    for m in range(d):
+        if p.shape[m] < 2:
+            continue
+        q = p.movedim(m, 0)
+        col = torch.empty_like(q)
+        col[1:-1] = (q[2:] - q[:-2]) * 0.5
+        col[0] = q[1] - q[0]
+        col[-1] = q[-1] - q[-2]
+        F[..., m] = col.movedim(0, m)
+    return F
+
+
 def _train_loop(m, num_iter, val_iter, ukl_iter, pis_l1, u_l1, callbacks, chunk_limit=None):
     """The iteration / validation / stop logic of ``Smoe.train`` (smoe.py:1485-1603), shared by both facades.  ``m`` supplies
     ``run_batched`` and four hooks: ``_quantize`` (quantize_params [+ rescaler], smoe.py:1498-1505,1539-1545),
@@ -1020,6 +1053,125 @@ class Smoe(_SmoeBase):
         if to_host:
             res = [t.cpu().numpy() for t in res]
         return tuple(res) if len(res) > 1 else res[0]
+
+    def _taps_each_arg(self, who, taps, foot, lead):
+        """``taps`` of ``sample_area_each`` as a contiguous uint8 ``[N, d]`` tensor on the device of ``foot`` (``[N, d, d]``):
+        ``"auto"`` (``blocks.footprint_taps_each``; for a tensor on the GPU the same integers are made there); a number, a
+        tuple or a list: one count or one per view axis for all points (checked as ``sample_area``'s -- a ``ValueError`` where
+        it would raise one --, then broadcast); an integer ``ndarray`` or tensor: one row per point, ``[..., d]`` exactly (a
+        count that is not 0 .. 255 becomes 0: void).  The two are told apart by type, never by shape."""
+        d = self.dim_domain
+        N = foot.shape[0]
+        if isinstance(taps, str):
+            if taps != "auto":
+                raise ValueError(f'{who}: taps must be "auto", a number, one per axis or an array [..., {d}]')
+            if foot.is_cuda:
+                return footprint_taps_each_torch(foot)
+            return torch.from_numpy(blk.footprint_taps_each(foot.numpy()))
+        if isinstance(taps, (int, np.integer, tuple, list)) and not isinstance(taps, bool):
+            try:
+                _, tp = blk.area_args(np.zeros((d, d), np.float32), taps, d)
+            except ValueError as e:
+                raise ValueError(f"{who}: {e}") from None
+            return torch.tensor(tp, dtype=torch.uint8, device=foot.device).repeat(N, 1)
+        tt = taps if torch.is_tensor(taps) else torch.from_numpy(np.ascontiguousarray(np.asarray(taps)))
+        if tuple(tt.shape) != lead + (d,) or tt.dtype.is_floating_point or tt.dtype == torch.bool:
+            raise ValueError(f"{who}: taps as an array must be integers {lead + (d,)}")
+        tt = tt.to(foot.device).reshape(N, d).to(torch.int64)
+        return torch.where((tt < 0) | (tt > 255), torch.zeros_like(tt), tt).to(torch.uint8).contiguous()
+
+    def sample_area_each(self, points, footprints, taps="auto", dtype=np.float32, quantized=False, want_mean=False,
+                         want_count=False, to_host=True, blend=0.0):
+        """``sample_area`` with a footprint of its own for every point, on the device (the engine's ``sample_area_each``;
+        include/smoe_hip.h: smoe_sample_area_each) -- a view whose magnification varies across the output: a perspective
+        view, a lens or stabilisation map, any dense lookup map.  ``points`` ``[..., d]`` and ``footprints`` ``[..., d, d]``
+        (arrays or device tensors; column ``m`` of a footprint is the edge vector of that sample's cell along view axis ``m``,
+        source pixels).  ``taps``: ``"auto"`` (``blocks.footprint_taps_each``: one tap per source pixel covered, per point),
+        a number or one per view axis (broadcast), or an integer array ``[..., d]``.  Positions: ``blocks.area_taps_each``.
+        A point is the result of ``sample_area`` with its footprint and taps, bit for bit.  A point whose taps are outside
+        1 .. 16, multiply to more than 64 or whose footprint is not finite is void: 0, mean 0, count 0.  Everything else,
+        and what is returned, is ``sample_area``'s."""
+        d = self.dim_domain
+        who = "sample_area_each"
+        bl = self._blend_arg(who, blend)
+        npdt = np.dtype(dtype)
+        if npdt not in (np.dtype(np.float32), np.dtype(np.uint8)):
+            raise ValueError(f"{who}: dtype must be float32 or uint8")
+        tdt = torch.uint8 if npdt == np.dtype(np.uint8) else torch.float32
+        eng = self._engine
+        if not hasattr(eng, "sample_area_each"):
+            raise NotImplementedError("this engine has no sample_area_each()")
+        dev = eng.device
+        pts, lead = self._points_arg(who, points, dev)
+        if torch.is_tensor(footprints):
+            foot = footprints
+        else:
+            fa = np.asarray(footprints)
+            if fa.dtype.kind not in "fiu":
+                raise ValueError(f"{who}: footprints must be numbers")
+            foot = torch.from_numpy(np.ascontiguousarray(fa, dtype=np.float32))
+        if tuple(foot.shape) != lead + (d, d) or not foot.dtype.is_floating_point:
+            raise ValueError(f"{who}: footprints must be floating point {lead + (d, d)}")
+        foot = foot.to(device=dev, dtype=torch.float32).reshape(-1, d, d).contiguous()
+        tp = self._taps_each_arg(who, taps, foot, lead)
+        params, active, center = self._whole_model(quantized)
+        res = eng.sample_area_each(params, active, self.grid, [int(v) for v in self.image.shape[:d]], pts, foot, tp,
+                                   blend=bl, dtype=tdt, want_mean=want_mean, want_count=want_count, center_grid=center)
+        res = list(res) if isinstance(res, tuple) else [res]
+        res[0] = res[0].reshape(lead + (self.channels,))
+        if want_mean:
+            res[1] = res[1].reshape(lead + (self.channels,))
+        if want_count:
+            res[-1] = res[-1].reshape(lead)
+        if to_host:
+            res = [t.cpu().numpy() for t in res]
+        return tuple(res) if len(res) > 1 else res[0]
+
+    def _ones_taps(self, who, taps):
+        """True where ``taps`` of a per-point view asks for nothing to average: None, or a number / one per axis, all ones."""
+        if taps is None:
+            return True
+        if not isinstance(taps, (int, np.integer, tuple, list)) or isinstance(taps, bool):
+            return False                                   # "auto", or an array / tensor of per-point counts
+        return self._taps_arg(who, taps, np.zeros((self.dim_domain, self.dim_domain))) is None
+
+    def render_projective(self, H, size, taps="auto", **options):
+        """A projective view of the model, anti-aliased: ``sample_area_each`` at ``blocks.projective_points(H, size)``.  ``H``
+        ``[d + 1, d + 1]`` maps the cell centre ``c = i + 0.5`` of output index ``i`` to ``(H[:d, :d] c + H[:d, d]) / (H[d, :d] .
+        c + H[d, d])`` in source pixels -- a homography; every sample is averaged over its own footprint, the analytic
+        Jacobian of the map there.  Returns the image ``[*size, C]``; samples behind the horizon (``s <= 0``) and where the
+        view leaves the image give 0.  ``taps``: ``"auto"`` (the default), a number or one per view axis; None or all ones:
+        ``sample(points)``.  ``options`` are ``sample_area_each``'s (``sample``'s with ``taps`` None)."""
+        try:
+            pts, foot, _ = blk.projective_points(H, size)
+        except ValueError as e:
+            raise ValueError(f"render_projective: {e}") from None
+        if self._ones_taps("render_projective", taps):
+            return self.sample(pts, **options)
+        return self.sample_area_each(pts, foot, taps=taps, **options)
+
+    def render_map(self, points, taps="auto", **options):
+        """A dense lookup map of the model, anti-aliased: ``points`` ``[*size, d]`` (an array or a device tensor) holds the
+        source position of every output sample -- a lens-distortion or stabilisation map, a fisheye or polar unwrapping --
+        and every sample is averaged over its own footprint ``blocks.map_footprints(points)`` (central differences of the map;
+        made on the device for a device tensor).  Returns ``[*size, C]``.  ``taps`` and ``options`` as in
+        ``render_projective``."""
+        d = self.dim_domain
+        if (points.dim() if torch.is_tensor(points) else np.ndim(points)) != d + 1 or tuple(points.shape)[-1] != d:
+            raise ValueError(f"render_map: points must be [*size, {d}] with {d} view axes")
+        if self._ones_taps("render_map", taps):
+            return self.sample(points, **options)
+        if torch.is_tensor(points):
+            if not points.dtype.is_floating_point:
+                raise ValueError("render_map: points must be floating point")
+            p32 = points.to(torch.float32)
+            foot = map_footprints_torch(p32) if p32.is_cuda else torch.from_numpy(blk.map_footprints(p32.numpy()))
+            return self.sample_area_each(p32, foot, taps=taps, **options)
+        pa = np.asarray(points)
+        if pa.dtype.kind not in "fiu":
+            raise ValueError("render_map: points must be numbers")
+        pa = pa.astype(np.float32)
+        return self.sample_area_each(pa, blk.map_footprints(pa), taps=taps, **options)
 
     def sample_grad(self, points, quantized=False, want_values=False, to_host=True, blend=0.0):
         """The model's exact spatial derivative at arbitrary positions, on the device (the engine's ``sample_grad``;

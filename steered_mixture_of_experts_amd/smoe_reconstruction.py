@@ -17,6 +17,11 @@ or a shear included; it works with ``--blend``, not with ``--window`` / ``--fram
 ``--taps N ...`` (one number or one per axis) or ``--taps auto`` with ``--affine`` or ``--window`` / ``--size`` averages every
 output sample over that many taps per axis inside its cell (``Smoe.sample_area``): a view coarser than the source that does
 not alias; per-block models only.
+``--homography H..`` (``(d + 1)^2`` numbers, row-major) with ``--size`` decodes a projective view with
+``Smoe.render_projective``: output cell centre ``c = i + 0.5`` shows the source position ``(H[:d, :d] c + H[:d, d]) / (H[d, :d] .
+c + H[d, d])``, every sample averaged over its OWN footprint (``Smoe.sample_area_each``; ``--taps`` defaults to ``auto`` here);
+samples behind the horizon are 0; it works with ``--blend``, not with ``--affine`` / ``--window`` / ``--frames`` / ``--scale``;
+per-block models only.
 """
 import argparse
 import os
@@ -49,7 +54,7 @@ _shared_engine_factory = None      # tests put the oracle-backed engine here; No
 
 
 def main(image_path, results_path, params_file, batches=1, bit_depths=(20, 18, 6, 10, 10), quant_params=False,
-         scale=None, frames=None, blend=None, window=None, size=None, affine=None, taps=None):
+         scale=None, frames=None, blend=None, window=None, size=None, affine=None, taps=None, homography=None):
     if len(bit_depths) != 5:
         raise ValueError("Number of bit depths must be five!")           # smoe_reconstruction.py:17-18
     orig, precision, _ = read_image(image_path)
@@ -60,7 +65,7 @@ def main(image_path, results_path, params_file, batches=1, bit_depths=(20, 18, 6
         if np.asarray(init_params['pis']).ndim == 1:
             raise ValueError("--taps needs a per-block model: this pickle holds a whole-image (shared-kernel) model, which "
                              "has no area-averaged decoder")
-        if affine is None and window is None and size is None:
+        if affine is None and window is None and size is None and homography is None:
             raise ValueError("--taps needs --affine or --window / --size (the view whose cells are averaged)")
     if results_path is not None and not os.path.exists(results_path):
         os.mkdir(results_path)
@@ -100,7 +105,28 @@ def main(image_path, results_path, params_file, batches=1, bit_depths=(20, 18, 6
         reconstruction = smoe.get_reconstruction()
     sc = [float(v) for v in np.atleast_1d(1.0 if scale is None else scale)]
     bl = [float(v) for v in np.atleast_1d(0.0 if blend is None else blend)]
-    if affine is not None:
+    if homography is not None:
+        # a projective view: every output sample at its own source position, averaged over its own footprint
+        # (Smoe.render_projective)
+        if not hasattr(smoe, "render_projective"):
+            raise ValueError("--homography needs a per-block model: this pickle holds a whole-image (shared-kernel) model, "
+                             "which has no point decoder")
+        d = smoe.dim_domain
+        if size is None:
+            raise ValueError("--homography needs --size (the output samples per axis)")
+        if affine is not None or window is not None or frames is not None or scale is not None:
+            raise ValueError("--homography does not go with --affine / --window / --frames / --scale (the matrix holds them)")
+        if len(homography) != (d + 1) * (d + 1):
+            raise ValueError(f"--homography takes {(d + 1) * (d + 1)} numbers: the rows of H")
+        if len(size) != d:
+            raise ValueError(f"--size takes one number per axis ({d})")
+        tph = "auto" if tp is None else tp
+        reconstruction = smoe.render_projective(np.asarray(homography, dtype=np.float64).reshape(d + 1, d + 1),
+                                                [int(v) for v in size], taps=tph, quantized=with_q, blend=bl)
+        reconstruction_path += "_proj" + "x".join(str(v) for v in reconstruction.shape[:d]) + _taps_suffix(tph)
+        if any(v != 0.0 for v in bl):
+            reconstruction_path += "_blend" + "x".join("%g" % v for v in bl)
+    elif affine is not None:
         # an affine view: every output sample at its own source position (Smoe.render_warp)
         if not hasattr(smoe, "render_warp"):
             raise ValueError("--affine needs a per-block model: this pickle holds a whole-image (shared-kernel) model, which "
@@ -201,8 +227,12 @@ def _parser():
     parser.add_argument('--affine', type=float, default=None, nargs='+',
                         help="decode an affine view of --size samples: the d (d + 1) numbers of [M | t], row-major; output "
                              "cell centre i + 0.5 shows source position M (i + 0.5) + t (per-block models only)")
+    parser.add_argument('--homography', type=float, default=None, nargs='+',
+                        help="decode a projective view of --size samples: the (d + 1)^2 numbers of H, row-major; output cell "
+                             "centre c = i + 0.5 shows source position (H[:d,:d] c + H[:d,d]) / (H[d,:d] . c + H[d,d]), averaged "
+                             "over its own footprint (--taps, default auto; per-block models only)")
     parser.add_argument('--taps', type=str, default=None, nargs='+',
-                        help="with --affine or --window / --size: average every output sample over this many taps per axis "
+                        help="with --affine, --homography or --window / --size: average every output sample over this many taps per axis "
                              "inside its cell (one number, one per axis, or auto = one per source pixel covered; 1 .. 16 each, "
                              "at most 64 in all; per-block models only)")
     return parser
