@@ -423,8 +423,8 @@ int smoe_sample_area(smoe_handle h, const smoe_params* p, const uint32_t* active
  * with a huge footprint -- |F| reaches thousands of pixels near a horizon -- sends its workgroup onto the unstaged path, with
  * the same bits (SMOE_SAMPLE_RECORDS applies).  Lanes run their own trip counts; points are never sorted or re-binned.
  * footprints and taps are loaded 16 / 4 bytes wide where their base is aligned so, element-wise otherwise: the same bits.
- * Limits: the equal-weight box filter, at most 16 taps per axis and 64 per point, per-block models only (there is no
- * smoe_shared_sample_area_each).
+ * Limits: the equal-weight box filter, at most 16 taps per axis and 64 per point, per-block models only (the counterpart for
+ * whole-image models is smoe_shared_sample_area_each).
  * num_points == 0 is a successful no-op.  SMOE_ERR_INVALID names the offending argument: smoe_sample_area's cases (its host
  * footprint / taps checks excepted), plus (num_points > 0) a null footprints or taps.  SMOE_ERR_UNSUPPORTED: as
  * smoe_sample_area. */
@@ -714,6 +714,42 @@ int smoe_shared_sample_area(smoe_shared_handle h, const smoe_params* p, const ui
                             const float* footprint, const int32_t* taps,
                             void* values, int32_t image_format,
                             float* mean, uint8_t* count, int32_t* batch, void* stream);
+
+/* smoe_shared_sample_area with a footprint and tap counts of its own for every point: a perspective view, a lens-distortion or
+ * stabilisation map, any dense lookup map of a whole-image model -- smoe_sample_area_each for the shared-kernel mode.  One fused
+ * kernel; nothing is materialised per tap.
+ *   p, lists, points, num_points, values, image_format, mean, count, batch     smoe_shared_sample_area's, with its outside rule,
+ *                            its lattice and the clamp of the index, "a centre outside with taps inside still gets their mean",
+ *                            batch = the batch of the centre (-1 outside), and no argmax
+ *   footprints               DEVICE [num_points, dim, dim] fp32, row-major per point, source pixels; any 4-byte address
+ *   taps                     DEVICE [num_points, dim] uint8; any address
+ * The result for point i is bit for bit the result of smoe_shared_sample_area called with that one point, footprints[i] and
+ * taps[i].  Written out in IEEE fp32 with F = footprints[i], n = taps[i] and tap multi-index j (0 <= j_m < n_m):
+ * o_m = (float)(2 j_m + 1 - n_m) / (float)(2 n_m), one correctly rounded division; t_l = x_l, then for m = 0 .. dim-1
+ * t_l = t_l + (F[l][m] * o_m), product and sum rounded separately (blocks.area_taps_each gives the positions bit for bit); each
+ * tap is resolved and evaluated exactly as a point of smoe_shared_sample_grad, with the list of the batch the tap lies in; taps
+ * are summed in row-major order of j, acc_c = acc_c + V_c and cnt += 1 for inside taps; mean_c = acc_c / (float)cnt, correctly
+ * rounded, 0 for cnt == 0.
+ * VOID points (smoe_sample_area_each's rule): a point is void if any taps[i][m] is outside 1 .. 16, if prod(taps[i]) > 64, or if
+ * any entry of footprints[i] is not finite.  A void point gives values 0, mean 0 and count 0; its batch is still the centre's
+ * batch; it never affects another point.  The host cannot check device arrays, so this is a defined result and there is no
+ * error code for it; whatever bytes the arrays hold, a point contributes at most 64 work items and the kernel indexes inside
+ * its tables.
+ * A workgroup takes a fixed run of 64 consecutive points -- the host plans the launch without reading device data -- and works
+ * through their taps in rounds of 256 (two axes) or 512 (three axes) work items; each round walks the distinct batches among its items as
+ * smoe_shared_sample_area does, and the owner lane of a point sums its taps in order across the rounds.  Neighbouring cells
+ * are cheap, scattered ones pay a batch walk per distinct batch and round; a small launch of many-tap points runs its rounds
+ * serially inside a workgroup (64 points of 64 taps: 16 or 8 rounds) where smoe_shared_sample_area would use 8 workgroups.  Offsets
+ * are 64-bit; stores are 16 bytes wide where values / mean / count / batch are 16-byte aligned.
+ * Limits: the equal-weight box filter, at most 16 taps per axis and 64 per point, no table (viewport) form.
+ * num_points == 0 is a successful no-op.  SMOE_ERR_INVALID names the offending argument: smoe_shared_sample_area's cases (its
+ * host footprint / taps checks excepted), plus (num_points > 0) a null footprints or taps.  SMOE_ERR_UNSUPPORTED:
+ * image_shape[l] > 2^24, SMOE_IMAGE_U8 values with precision > 8, 2^31 or more workgroups, more than 160 KB of LDS. */
+int smoe_shared_sample_area_each(smoe_shared_handle h, const smoe_params* p, const uint32_t* lists,
+                                 const float* points, int64_t num_points,
+                                 const float* footprints, const uint8_t* taps,
+                                 void* values, int32_t image_format,
+                                 float* mean, uint8_t* count, int32_t* batch, void* stream);
 
 /* run_batched(train=True) minus train_op: forward + tf.gradients of the batches, accumulated into
  * the handle's gradient buffer (accum_ops, smoe.py:1150); kernel lists pruned (smoe.py:1763-1766).

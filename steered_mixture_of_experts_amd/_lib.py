@@ -33,7 +33,7 @@ EXPORTS = (
     "smoe_render", "smoe_shared_render", "smoe_last_fit_variant", "smoe_render_blend",
     "smoe_render_view", "smoe_sample", "smoe_shared_sample", "smoe_shared_render_view", "smoe_sample_grad",
     "smoe_shared_sample_grad", "smoe_shared_render_view_grad", "smoe_sample_area", "smoe_shared_sample_area",
-    "smoe_sample_area_each",
+    "smoe_sample_area_each", "smoe_shared_sample_area_each",
 )
 
 
@@ -149,6 +149,7 @@ def load() -> C.CDLL:
                                                  C.POINTER(C.c_void_p), fp, fp, fp, vp]
     lib.smoe_shared_sample_area.argtypes = [vp, C.POINTER(SmoeParams), fp, fp, C.c_int64, C.POINTER(C.c_float),
                                             C.POINTER(C.c_int32), fp, i32, fp, fp, fp, vp]
+    lib.smoe_shared_sample_area_each.argtypes = [vp, C.POINTER(SmoeParams), fp, fp, C.c_int64, fp, fp, fp, i32, fp, fp, fp, vp]
     lib.smoe_shared_accumulate.argtypes =[vp, i32, i32, fp, C.POINTER(SmoeParams), fp, fp, fp, vp]
     lib.smoe_shared_apply.argtypes = [vp, C.POINTER(SmoeParams), C.POINTER(SmoeAdamState), vp]
     lib.smoe_shared_grad_buffer.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]

@@ -1923,6 +1923,51 @@ int smoe_shared_sample_area(smoe_shared_handle h, const smoe_params* p, const ui
 #endif
 }
 
+int smoe_shared_sample_area_each(smoe_shared_handle h, const smoe_params* p, const uint32_t* lists, const float* points,
+                                 int64_t num_points, const float* footprints, const uint8_t* taps, void* values,
+                                 int32_t image_format, float* mean, uint8_t* count, int32_t* batch, void* stream) {
+    const std::string fn = "smoe_shared_sample_area_each";
+    if (!h) return fail(SMOE_ERR_INVALID, fn + ": null handle");
+    if (!params_ok(p)) return fail(SMOE_ERR_INVALID, fn + ": p (all six parameter tensors) is required");
+    if (image_format != SMOE_IMAGE_F32 && image_format != SMOE_IMAGE_U8)
+        return fail(SMOE_ERR_INVALID, fn + ": image_format must be SMOE_IMAGE_F32 or SMOE_IMAGE_U8");
+    if (num_points < 0) return fail(SMOE_ERR_INVALID, fn + ": num_points must be >= 0");
+    if (num_points == 0) return SMOE_OK;
+    if (!points) return fail(SMOE_ERR_INVALID, fn + ": points is required");
+    if (!footprints) return fail(SMOE_ERR_INVALID, fn + ": footprints is required");
+    if (!taps) return fail(SMOE_ERR_INVALID, fn + ": taps is required");
+    if (!values && !mean) return fail(SMOE_ERR_INVALID, fn + ": values or mean is required");
+    const int D = h->cfg.dim;
+    for (int l = 0; l < D; ++l)
+        if (h->cfg.image_shape[l] > (1 << 24))
+            return fail(SMOE_ERR_UNSUPPORTED, fn + ": image_shape must not exceed 2^24 on any axis (batch origins are exact in fp32)");
+    if (values && image_format == SMOE_IMAGE_U8 && h->cfg.precision > 8)
+        return fail(SMOE_ERR_UNSUPPORTED, fn + ": SMOE_IMAGE_U8 needs precision <= 8");
+    smoe::SharedSampleAreaEachArgs q;
+    std::memset(&q, 0, sizeof q);
+    q.s.points = points; q.s.num_points = num_points;
+    for (int l = 0; l < SMOE_MAX_DIM; ++l) q.s.ext[l] = 1;
+    shared_sample_model(h, p, lists, q.s);
+    decoder_planes(q.s, values, image_format, (int32_t*)nullptr, h->kc);
+    q.footprints = footprints; q.taps = taps;
+    q.mean = mean; q.count = count; q.batch = batch;
+    q.vec_mean = ((uintptr_t)mean % 16 == 0) ? 1 : 0;
+    q.vec_cnt = ((uintptr_t)count % 16 == 0) ? 1 : 0;
+    q.vec_bat = ((uintptr_t)batch % 16 == 0) ? 1 : 0;
+    smoe::RenderLayout lay;
+    const char* const unsupported = "the launch would need 2^31 or more workgroups, or more than 160 KB of LDS";
+    int rc = decoder_launched(fn, smoe::shared_sample_area_each_layout(D, h->cfg.channels, q.s.K, num_points, lay), unsupported);
+    if (rc != SMOE_OK) return rc;
+#if !SMOE_HOST_TEST
+    rc = shared_sample_ready(h, fn, p, stream);
+    if (rc) return rc;
+    return decoder_launched(fn, smoe::launch_shared_sample_area_each(q, D, h->cfg.channels, lay, (hipStream_t)stream), unsupported);
+#else
+    (void)stream;
+    return SMOE_OK;
+#endif
+}
+
 // gather: sum the batches' rows into the gradient buffer right away (what smoe_shared_grad_buffer hands out for the
 // all-reduce); smoe_shared_fit leaves it to the step kernel (one launch less per iteration)
 static int shared_accumulate_impl(smoe_shared_handle h, int32_t first_batch, int32_t num_batches, const float* target,

@@ -412,6 +412,18 @@ struct SharedSampleAreaArgs {
     int vec_mean, vec_cnt, vec_bat;   // the plane's base is 16-byte aligned: vector stores
 };
 
+// smoe_shared_sample_area_each (smoe_shared_sample_area_each.hip.h): smoe_shared_sample_area with a footprint and tap counts of
+// its own for every point of `s` (list mode only).  s, mean, count, batch as in SharedSampleAreaArgs.
+struct SharedSampleAreaEachArgs {
+    SharedSampleArgs s;
+    const float* footprints;  // [N, dim, dim] row-major per point, source pixels; any 4-byte address
+    const uint8_t* taps;      // [N, dim] taps per view axis; any address
+    float* mean;              // [N, C] the mean before the lattice, or null
+    uint8_t* count;           // [N] taps inside the image, or null
+    int32_t* batch;           // [N] global id of the batch that owns the centre, -1 = centre outside; or null
+    int vec_mean, vec_cnt, vec_bat;   // the plane's base is 16-byte aligned: vector stores
+};
+
 // Per-kernel sum over the batches of the current pass, in a fixed order (lane = batch mod 64 ascending, then a butterfly
 // over the lanes): racc[k][PK] and nact[k] are OVERWRITTEN -- bit-identical from run to run and for every split of the
 // batches of a rank over smoe_shared_accumulate calls.
@@ -499,6 +511,9 @@ hipError_t launch_shared_sample_grad(const SharedSampleGradArgs& q, int D, int C
 // the same pair for smoe_shared_sample_area; T = prod(taps), 1 .. SAMPLE_AREA_TAPS.  The launch fills q.ppw
 hipError_t shared_sample_area_layout(int D, int C, int K, int T, long long num_points, RenderLayout& g);
 hipError_t launch_shared_sample_area(const SharedSampleAreaArgs& q, int D, int C, const RenderLayout& g, hipStream_t st);
+// the same pair for smoe_shared_sample_area_each: a workgroup takes a fixed run of points, so the plan reads no device data
+hipError_t shared_sample_area_each_layout(int D, int C, int K, long long num_points, RenderLayout& g);
+hipError_t launch_shared_sample_area_each(const SharedSampleAreaEachArgs& q, int D, int C, const RenderLayout& g, hipStream_t st);
 
 const Variant* variants(int* count);
 hipError_t launch_readmit(const ReadmitArgs& a, int D, hipStream_t st);

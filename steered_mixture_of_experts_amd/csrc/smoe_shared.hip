@@ -1148,6 +1148,8 @@ __global__ void shared_readmit_kernel(SharedReadmitArgs a) {
 #include "smoe_shared_sample_grad.hip.h"
 // and the area-averaged decode at the same points (shared_sample_area_kernel, launch_shared_sample_area)
 #include "smoe_shared_sample_area.hip.h"
+// and the same with a footprint of its own per point (shared_sample_area_each_kernel, launch_shared_sample_area_each)
+#include "smoe_shared_sample_area_each.hip.h"
 
 namespace smoe {
 

@@ -853,6 +853,34 @@ class SharedEngine(_Engine):
         res = (out,) + ((mean,) if want_mean else ()) + ((cnt,) if want_count else ()) + ((bk,) if want_batch else ())
         return res if len(res) > 1 else out
 
+    def sample_area_each(self, params, lists, points, footprints, taps, out=None, dtype=torch.float32, want_mean=False,
+                         want_count=False, want_batch=False):
+        """Anti-aliased point decode with a footprint of its own per point (include/smoe_hip.h:
+        smoe_shared_sample_area_each): ``sample_area`` where point ``i`` has the footprint ``footprints[i]`` and the tap counts
+        ``taps[i]`` -- contiguous device tensors, float32 ``[N, d, d]`` and uint8 ``[N, d]`` (``blocks.area_taps_each`` states
+        the positions).  A point whose taps are outside 1 .. 16, multiply to more than 64 or whose footprint is not finite is
+        void: 0 / 0 / count 0.  Everything else, and what is returned, is ``sample_area``'s."""
+        who = "sample_area_each"
+        N = self._check_points(who, points, lists)
+        d = self.cfg.dim
+        if not torch.is_tensor(footprints) or tuple(footprints.shape) != (N, d, d) or footprints.dtype != torch.float32 \
+                or not footprints.is_contiguous() or footprints.device != self.device:
+            raise ValueError(f"{who}: footprints must be a contiguous float32 tensor [{N}, {d}, {d}] on {self.device}")
+        if not torch.is_tensor(taps) or tuple(taps.shape) != (N, d) or taps.dtype != torch.uint8 or not taps.is_contiguous() \
+                or taps.device != self.device:
+            raise ValueError(f"{who}: taps must be a contiguous uint8 tensor [{N}, {d}] on {self.device}")
+        out, fmt, _ = self._dense_planes(who, (N,), out, dtype, False)
+        mean = torch.empty((N, self.cfg.channels), dtype=torch.float32, device=self.device) if want_mean else None
+        cnt = torch.empty((N,), dtype=torch.uint8, device=self.device) if want_count else None
+        bk = torch.empty((N,), dtype=torch.int32, device=self.device) if want_batch else None
+        if N > 0:
+            cp = self._cparams(params)
+            _lib.check(self.lib.smoe_shared_sample_area_each(self._h, C.byref(cp), _ptr(lists), _ptr(points), N,
+                                                             _ptr(footprints), _ptr(taps), _ptr(out), fmt, _ptr(mean),
+                                                             _ptr(cnt), _ptr(bk), self._stream()))
+        res = (out,) + ((mean,) if want_mean else ()) + ((cnt,) if want_count else ()) + ((bk,) if want_batch else ())
+        return res if len(res) > 1 else out
+
     def render_view_grad(self, params, lists, axes, batches, out=None, want_values=False, want_batch=False):
         """Viewport derivative (include/smoe_hip.h: smoe_shared_render_view_grad): ``sample_grad`` on the dense view of
         ``render_view``'s tables, ``[*E, d, C]``; the other planes ``[*E, C]`` and ``[*E]``."""

@@ -348,6 +348,40 @@ class _SmoeBase:
                 raise ValueError(f"{who}: {e}") from None
         return None if all(v == 1 for v in tp) else tp
 
+    def _taps_each_arg(self, who, taps, foot, lead):
+        """``taps`` of ``sample_area_each`` as a contiguous uint8 ``[N, d]`` tensor on the device of ``foot`` (``[N, d, d]``):
+        ``"auto"`` (``blocks.footprint_taps_each``; for a tensor on the GPU the same integers are made there); a number, a
+        tuple or a list: one count or one per view axis for all points (checked as ``sample_area``'s -- a ``ValueError`` where
+        it would raise one --, then broadcast); an integer ``ndarray`` or tensor: one row per point, ``[..., d]`` exactly (a
+        count that is not 0 .. 255 becomes 0: void).  The two are told apart by type, never by shape."""
+        d = self.dim_domain
+        N = foot.shape[0]
+        if isinstance(taps, str):
+            if taps != "auto":
+                raise ValueError(f'{who}: taps must be "auto", a number, one per axis or an array [..., {d}]')
+            if foot.is_cuda:
+                return footprint_taps_each_torch(foot)
+            return torch.from_numpy(blk.footprint_taps_each(foot.numpy()))
+        if isinstance(taps, (int, np.integer, tuple, list)) and not isinstance(taps, bool):
+            try:
+                _, tp = blk.area_args(np.zeros((d, d), np.float32), taps, d)
+            except ValueError as e:
+                raise ValueError(f"{who}: {e}") from None
+            return torch.tensor(tp, dtype=torch.uint8, device=foot.device).repeat(N, 1)
+        tt = taps if torch.is_tensor(taps) else torch.from_numpy(np.ascontiguousarray(np.asarray(taps)))
+        if tuple(tt.shape) != lead + (d,) or tt.dtype.is_floating_point or tt.dtype == torch.bool:
+            raise ValueError(f"{who}: taps as an array must be integers {lead + (d,)}")
+        tt = tt.to(foot.device).reshape(N, d).to(torch.int64)
+        return torch.where((tt < 0) | (tt > 255), torch.zeros_like(tt), tt).to(torch.uint8).contiguous()
+
+    def _ones_taps(self, who, taps):
+        """True where ``taps`` of a per-point view asks for nothing to average: None, or a number / one per axis, all ones."""
+        if taps is None:
+            return True
+        if not isinstance(taps, (int, np.integer, tuple, list)) or isinstance(taps, bool):
+            return False                                   # "auto", or an array / tensor of per-point counts
+        return self._taps_arg(who, taps, np.zeros((self.dim_domain, self.dim_domain))) is None
+
     def _render(self, scale, samples_per_block, dtype, quantized, want_argmax, to_host, use_lists=True, blend=None):
         """``render`` of both modes.  Hooks: ``_local_rparams``, ``_render_lists(quantized)``, ``_render_grid(m)`` ->
         (tile grid, output extent, one sample table per axis), ``_engine_render`` and, with ``_block_local_ids``,
@@ -1054,32 +1088,6 @@ class Smoe(_SmoeBase):
             res = [t.cpu().numpy() for t in res]
         return tuple(res) if len(res) > 1 else res[0]
 
-    def _taps_each_arg(self, who, taps, foot, lead):
-        """``taps`` of ``sample_area_each`` as a contiguous uint8 ``[N, d]`` tensor on the device of ``foot`` (``[N, d, d]``):
-        ``"auto"`` (``blocks.footprint_taps_each``; for a tensor on the GPU the same integers are made there); a number, a
-        tuple or a list: one count or one per view axis for all points (checked as ``sample_area``'s -- a ``ValueError`` where
-        it would raise one --, then broadcast); an integer ``ndarray`` or tensor: one row per point, ``[..., d]`` exactly (a
-        count that is not 0 .. 255 becomes 0: void).  The two are told apart by type, never by shape."""
-        d = self.dim_domain
-        N = foot.shape[0]
-        if isinstance(taps, str):
-            if taps != "auto":
-                raise ValueError(f'{who}: taps must be "auto", a number, one per axis or an array [..., {d}]')
-            if foot.is_cuda:
-                return footprint_taps_each_torch(foot)
-            return torch.from_numpy(blk.footprint_taps_each(foot.numpy()))
-        if isinstance(taps, (int, np.integer, tuple, list)) and not isinstance(taps, bool):
-            try:
-                _, tp = blk.area_args(np.zeros((d, d), np.float32), taps, d)
-            except ValueError as e:
-                raise ValueError(f"{who}: {e}") from None
-            return torch.tensor(tp, dtype=torch.uint8, device=foot.device).repeat(N, 1)
-        tt = taps if torch.is_tensor(taps) else torch.from_numpy(np.ascontiguousarray(np.asarray(taps)))
-        if tuple(tt.shape) != lead + (d,) or tt.dtype.is_floating_point or tt.dtype == torch.bool:
-            raise ValueError(f"{who}: taps as an array must be integers {lead + (d,)}")
-        tt = tt.to(foot.device).reshape(N, d).to(torch.int64)
-        return torch.where((tt < 0) | (tt > 255), torch.zeros_like(tt), tt).to(torch.uint8).contiguous()
-
     def sample_area_each(self, points, footprints, taps="auto", dtype=np.float32, quantized=False, want_mean=False,
                          want_count=False, to_host=True, blend=0.0):
         """``sample_area`` with a footprint of its own for every point, on the device (the engine's ``sample_area_each``;
@@ -1126,14 +1134,6 @@ class Smoe(_SmoeBase):
         if to_host:
             res = [t.cpu().numpy() for t in res]
         return tuple(res) if len(res) > 1 else res[0]
-
-    def _ones_taps(self, who, taps):
-        """True where ``taps`` of a per-point view asks for nothing to average: None, or a number / one per axis, all ones."""
-        if taps is None:
-            return True
-        if not isinstance(taps, (int, np.integer, tuple, list)) or isinstance(taps, bool):
-            return False                                   # "auto", or an array / tensor of per-point counts
-        return self._taps_arg(who, taps, np.zeros((self.dim_domain, self.dim_domain))) is None
 
     def render_projective(self, H, size, taps="auto", **options):
         """A projective view of the model, anti-aliased: ``sample_area_each`` at ``blocks.projective_points(H, size)``.  ``H``
@@ -1716,6 +1716,82 @@ class SharedSmoe(_SmoeBase):
         if to_host:
             res = [t.cpu().numpy() for t in res]
         return tuple(res) if len(res) > 1 else res[0]
+
+    def eval_points_area_each(self, points, footprints, taps="auto", dtype=np.float32, quantized=False, want_mean=False,
+                              want_count=False, to_host=True, use_lists=True):
+        """``eval_points_area`` with a footprint of its own for every point, on the device (the engine's ``sample_area_each``;
+        include/smoe_hip.h: smoe_shared_sample_area_each) -- ``Smoe.sample_area_each`` for a whole-image model: a view whose
+        magnification varies across the output, a perspective view, a lens or stabilisation map, any dense lookup map.
+        ``points`` ``[..., d]`` and ``footprints`` ``[..., d, d]`` (arrays or device tensors; column ``m`` of a footprint is the
+        edge vector of that sample's cell along view axis ``m``, source pixels).  ``taps``: ``"auto"``
+        (``blocks.footprint_taps_each``: one tap per source pixel covered, per point), a number or one per view axis
+        (broadcast), or an integer array ``[..., d]``.  Positions: ``blocks.area_taps_each``.  A point is the result of
+        ``eval_points_area`` with its footprint and taps, bit for bit.  A point whose taps are outside 1 .. 16, multiply to
+        more than 64 or whose footprint is not finite is void: 0, mean 0, count 0.  Everything else, and what is returned, is
+        ``eval_points_area``'s."""
+        d = self.dim_domain
+        who = "eval_points_area_each"
+        tdt, eng, params, lists = self._eval_model(who, dtype, quantized, use_lists, "sample_area_each")
+        pts, lead = self._eval_points_arg(who, points, eng.device)
+        if torch.is_tensor(footprints):
+            foot = footprints
+        else:
+            fa = np.asarray(footprints)
+            if fa.dtype.kind not in "fiu":
+                raise ValueError(f"{who}: footprints must be numbers")
+            foot = torch.from_numpy(np.ascontiguousarray(fa, dtype=np.float32))
+        if tuple(foot.shape) != lead + (d, d) or not foot.dtype.is_floating_point:
+            raise ValueError(f"{who}: footprints must be floating point {lead + (d, d)}")
+        foot = foot.to(device=eng.device, dtype=torch.float32).reshape(-1, d, d).contiguous()
+        tp = self._taps_each_arg(who, taps, foot, lead)
+        res = eng.sample_area_each(params, lists, pts, foot, tp, dtype=tdt, want_mean=want_mean, want_count=want_count)
+        res = list(res) if isinstance(res, tuple) else [res]
+        res[0] = res[0].reshape(lead + (self.channels,))
+        if want_mean:
+            res[1] = res[1].reshape(lead + (self.channels,))
+        if want_count:
+            res[-1] = res[-1].reshape(lead)
+        if to_host:
+            res = [t.cpu().numpy() for t in res]
+        return tuple(res) if len(res) > 1 else res[0]
+
+    def eval_projective(self, H, size, taps="auto", **options):
+        """A projective view of the model, anti-aliased: ``eval_points_area_each`` at ``blocks.projective_points(H, size)`` --
+        ``Smoe.render_projective`` for a whole-image model.  ``H`` ``[d + 1, d + 1]`` maps the cell centre ``c = i + 0.5`` of
+        output index ``i`` to ``(H[:d, :d] c + H[:d, d]) / (H[d, :d] . c + H[d, d])`` in source pixels; every sample is
+        averaged over its own footprint, the analytic Jacobian of the map there.  Returns the image ``[*size, C]``; samples
+        behind the horizon and where the view leaves the image give 0.  ``taps``: ``"auto"`` (the default), a number or one
+        per view axis; None or all ones: ``eval_points(points)``.  ``options`` are ``eval_points_area_each``'s
+        (``eval_points``'s with ``taps`` None)."""
+        try:
+            pts, foot, _ = blk.projective_points(H, size)
+        except ValueError as e:
+            raise ValueError(f"eval_projective: {e}") from None
+        if self._ones_taps("eval_projective", taps):
+            return self.eval_points(pts, **options)
+        return self.eval_points_area_each(pts, foot, taps=taps, **options)
+
+    def eval_map(self, points, taps="auto", **options):
+        """A dense lookup map of the model, anti-aliased -- ``Smoe.render_map`` for a whole-image model: ``points``
+        ``[*size, d]`` (an array or a device tensor) holds the source position of every output sample, and every sample is
+        averaged over its own footprint ``blocks.map_footprints(points)`` (central differences of the map; made on the device
+        for a device tensor).  Returns ``[*size, C]``.  ``taps`` and ``options`` as in ``eval_projective``."""
+        d = self.dim_domain
+        if (points.dim() if torch.is_tensor(points) else np.ndim(points)) != d + 1 or tuple(points.shape)[-1] != d:
+            raise ValueError(f"eval_map: points must be [*size, {d}] with {d} view axes")
+        if self._ones_taps("eval_map", taps):
+            return self.eval_points(points, **options)
+        if torch.is_tensor(points):
+            if not points.dtype.is_floating_point:
+                raise ValueError("eval_map: points must be floating point")
+            p32 = points.to(torch.float32)
+            foot = map_footprints_torch(p32) if p32.is_cuda else torch.from_numpy(blk.map_footprints(p32.numpy()))
+            return self.eval_points_area_each(p32, foot, taps=taps, **options)
+        pa = np.asarray(points)
+        if pa.dtype.kind not in "fiu":
+            raise ValueError("eval_map: points must be numbers")
+        pa = pa.astype(np.float32)
+        return self.eval_points_area_each(pa, blk.map_footprints(pa), taps=taps, **options)
 
     # -- the exact spatial derivative at the same points ----------------------------------------
     @staticmethod
